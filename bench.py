@@ -6,9 +6,16 @@ Default workload = BASELINE.json configs[2], the one `metric` is quoted on: Shap
 depth-8 VAE octree), batch 8 per GPU, DDIM eps-branch.  One step = one full U-Net forward (sparse hr net + the
 nested dense lr net) + the DDIM update for the whole batch.  Inputs are resident in HBM before the timed region.
 fp32 storage; default contraction fp16x3 (fp16 hi/lo operand pairs, three fp16 MFMAs per product, fp32 accumulate:
-the fp32 reference's rounding class); exact fp32 MFMA and the bf16-pair variant are timed beside it.
+the fp32 reference's rounding class); with --full, exact fp32 MFMA and the bf16-pair variant are timed beside it.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload hr|lr|hr_cond|feature]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload hr|lr|hr_cond|feature] [--full]
+                    [--dump-outputs DIR]
+
+A plain run sets up, warms up, times K steps and prints the line.  --full adds everything else the benchmark
+measures or checks, after the timed steps: the per-launch roofline passes, the side runs (other precisions and launch
+shapes), the sustained run, the lanes A/B, the MFMA and gather probes, the one-rank RCCL group at world 1, the parity
+spot check and the CPU baseline.  --dump-outputs DIR writes the state x the last timed step left (what
+sampler.sample_loop returns) to DIR/x.npy; the inputs are seeded, so two builds can be compared output for output.
 
 `--gpus N` (N > 1) starts N ranks by itself (re-executes under torch.distributed.run on 127.0.0.1) unless it is
 already running under a launcher (WORLD_SIZE set).  Prints ONE JSON line on rank 0 (DESIGN.md "Measurement").
@@ -100,10 +107,9 @@ class Workload:
         self.net = self.net.to(dev).eval()
         self.bcast_bytes = dist.broadcast_module_(self.net, src=0)        # the only collective: weights, once
         self.doc = None
-        self.setup_ms = self.setup_warm_ms = 0.0
+        self.setup_ms = 0.0
         if w['tree']:
             _, self.doc, self.setup_ms = build_tree(w['tree'], batch, dev)          # first call: includes lazy code loading
-            self.setup_warm_ms = build_tree(w['tree'], batch, dev)[2]               # what every later batch of shapes pays
             self.shape = (self.doc.total_num, configs.CONFIGS[w['config']]['input_channels'][-1 if self.stage == 'feature' else 1])
         else:
             self.shape = (batch, 8, 16, 16, 16)
@@ -230,6 +236,31 @@ def replay_lanes(wl, first, n):
                 if L.noise_s is not None:
                     L.noise_s.normal_()
                 L.graph.replay()
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(wl, out_dir):
+    """DIR/x.npy (float32): the state x after the last timed step, the array sampler.sample_loop hands its caller (lanes
+    put back in batch order).  An x above DUMP_MAX_BYTES is written as a fixed seeded sample of whole rows, the same
+    rows for the same arguments."""
+    import numpy as np
+    if wl.lanes:
+        x = wl.x_init.clone()
+        for L in wl.lanes:
+            x.index_copy_(0, L.rows, L.x)
+    else:
+        x = wl.x
+    x = x.detach().float().cpu()
+    n_rows = None
+    if x.numel() * 4 > DUMP_MAX_BYTES:
+        keep = DUMP_MAX_BYTES // (4 * x[0].numel())
+        rows = torch.randperm(x.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+        x, n_rows = x.index_select(0, rows), keep
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, 'x.npy'), x.numpy())
+    return {'dir': out_dir, 'arrays': {'x': list(x.shape)}, 'rows_sampled': n_rows}
 
 
 def timed(fn, n_sync=True):
@@ -596,15 +627,21 @@ def main():
     ap.add_argument('--workload', default='hr', choices=sorted(WORKLOADS))
     ap.add_argument('--batch', type=int, default=None, help='shapes per GPU (weak scaling)')
     ap.add_argument('--precision', default='fp16x3', choices=['fp16x3', 'bf16x3', 'fp32', 'fp16'])
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also run every side measurement and check (see the module docstring)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the state the last timed step left to DIR/x.npy (float32)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the parity spot check and CPU baseline')
     ap.add_argument('--eager', action='store_true', help='time eager launches instead of hipGraph replay')
     ap.add_argument('--lanes', type=int, default=None, help='lanes of a graph stage (default: sampler.lane_count; 1 = one stream)')
     ap.add_argument('--lane-cus', type=int, default=None, help='compute units a persistent launch of a lane is planned for')
-    ap.add_argument('--no-extras', action='store_true', help='skip the fp32 / old-kernel / graph / sustained side runs')
-    ap.add_argument('--layers', action='store_true', help='add the per-layer table of the fused GraphConv launches')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: skip the fp32 / old-kernel / graph / sustained side runs')
+    ap.add_argument('--layers', action='store_true', help='with --full: add the per-layer table of the fused GraphConv launches')
     ap.add_argument('--bootstrap-only', action='store_true',
                     help='initialise the ranks, broadcast a dummy tensor, print the rank table and exit (CPU test)')
     args = ap.parse_args()
+    if args.layers and not args.full:
+        ap.error('--layers needs --full (the per-launch timings come from the --full passes)')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # no launcher: start one rank per GPU ourselves
@@ -645,8 +682,8 @@ def main():
         dist.barrier()
         dist.shutdown()
         return
-    rccl_note = None
-    if world == 1 and torch.cuda.is_available():
+    rccl_note = 'none at world 1 (--full runs the collectives through a one-rank RCCL group)'
+    if world == 1 and torch.cuda.is_available() and args.full:
         # one GPU: still run the collectives of the multi-GPU path (weight broadcast, timing reductions, barriers) through
         # RCCL, on a one-rank group, so that a single-GPU box executes the same device path the 8-GPU run depends on
         try:
@@ -672,14 +709,19 @@ def main():
     if wl.lanes:
         ops.set_lane_cus(wl.sampler.LANE_CUS if args.lane_cus is None else args.lane_cus)
     first_ms = 1e3 * timed(lambda: wl.run(0, 1))        # first step of the process: weight packing + per-doctree tables
-    new_tree_first_ms = None
-    if wl.doc is not None and rank == 0:
+    new_tree_first_ms = setup_warm_ms = None
+    if wl.doc is not None and rank == 0 and args.full:
+        setup_warm_ms = build_tree(w['tree'], batch, dev)[2]        # what every later batch of shapes pays
         # what every LATER batch of shapes pays on its first step: a new doctree (its lazily built tables and operand
         # slabs) with the weights already packed
         doc_keep, lanes_keep = wl.doc, wl.lanes
         wl.set_doc(build_tree(w['tree'], batch, dev)[1])
         new_tree_first_ms = 1e3 * timed(lambda: wl.run(0, 1))
         wl.doc, wl.lanes = doc_keep, lanes_keep
+    elif wl.doc is not None and rank == 0 and not wl.lanes:
+        # --full's later-batch step advances x on an identical tree: a plain run takes that step on its own tree, so
+        # that its timed steps start from the state a --full run's do and both write the same outputs
+        wl.run(0, 1)
     wl.run(1, max(W - 1, 0))
     torch.cuda.synchronize()
     steady_ms = 1e3 * timed(lambda: wl.run(W, 1))
@@ -744,7 +786,7 @@ def main():
 
     # ---- the contract region: exactly K steps, barrier + synchronize on both sides, MAX over ranks --------
     prof = []
-    if replay is None:
+    if replay is None and args.full:
         ops.GRAPHCONV_PROFILE = prof
     dist.barrier()
     torch.cuda.synchronize()
@@ -760,9 +802,10 @@ def main():
     dt = dist.max_over_ranks(dt_local, dev)
     rank_ms = dist.gather_floats(1e3 * dt_local / K, dev)
     ms_step = 1e3 * dt / K
+    dumped = dump_outputs(wl, args.dump_outputs) if args.dump_outputs and rank == 0 else None
     eager_ms = None
     dt_prof = dt
-    if replay is not None:
+    if replay is not None and args.full:
         # HIP events cannot be recorded inside a graph replay: the per-launch timings of the roofline come from an
         # eager re-run of the same K steps right after the timed region (same kernels, same inputs)
         # (lanes: one after another in this pass, so that an event pair brackets a kernel that has the chip to itself)
@@ -775,7 +818,7 @@ def main():
     # per-class accounting of everything that is not the fused GraphConv: a second eager pass with an event pair
     # around every entry-point call (kept apart from the pass above so that its brackets stay undisturbed)
     tail, n_tail = [], max(2, min(K, 5))
-    if rank == 0 and not args.no_extras:
+    if rank == 0 and args.full and not args.no_extras:
         wl.serial = True
         _lib.PROFILE = tail
         dt_tail = timed(lambda: wl.run(W + 1, n_tail))
@@ -786,8 +829,8 @@ def main():
     ops.raise_on_sync_error(dev)            # a flag wait of the persistent launch gave up: the timing would be void
 
     res = None
-    if rank == 0:
-        bf = args.precision
+    bf = args.precision
+    if rank == 0 and args.full:
         peak = PEAKS[bf]
         planes_kind = {'fp16x3': 'graph2', 'bf16x3': 'graph2', 'fp16': 'graph2h'}.get(bf)
         dom = profile_summary(prof, dt_prof, (planes_kind,), peak) if planes_kind else None
@@ -877,6 +920,7 @@ def main():
                                                  'read once, the CSR, the output (ops.graphconv_narrow_out)'} for r_ in narrow]
         roof['all_graphconv_launches'] = graph_only
         roof['gridconv_27tap_launches'] = grid_only
+    if rank == 0:
         res = {
             'metric': 'denoising-steps/sec (depth-8 octree, batch 8)', 'value': world * K / dt,
             'unit': 'steps/s', 'n_gpus': world, 'steps': K, 'warmup': W, 'ms_per_step': ms_step,
@@ -896,7 +940,6 @@ def main():
                               'matrix-bound and HBM-bound launches overlap; `roofline` and `roofline_tail` are per-launch event '
                               'timings of an eager pass with the lanes one after another (a kernel alone on the chip, at the '
                               'lane\'s row count); --lanes 1 runs the whole batch on one stream'} if wl.lanes else None,
-            'eager_ms_per_step': eager_ms if replay is not None else ms_step,
             'config': {'workload': w['desc'] % batch, 'name': args.workload, 'config': w['config'],
                        'batch_per_gpu': batch, 'nodes_per_gpu': wl.doc.total_num if wl.doc else None,
                        'parallelism': 'batch-shard x%d, one RCCL weight broadcast (%d bytes)' % (world, wl.bcast_bytes)},
@@ -907,21 +950,25 @@ def main():
             'host_cpu_ms_per_step': {'issue': 1e3 * cpu_issue / K, 'issue_plus_sync_wait': 1e3 * cpu_total / K},
             'weight_broadcast_bytes': wl.bcast_bytes,
             'rccl': rccl_note if world == 1 else 'nccl (RCCL) group of %d ranks' % world,
-            'per_shape_setup': {'octree_and_dual_graph_ms': wl.setup_warm_ms, 'octree_and_dual_graph_first_call_ms': wl.setup_ms,
+            'per_shape_setup': {'octree_and_dual_graph_ms': setup_warm_ms, 'octree_and_dual_graph_first_call_ms': wl.setup_ms,
                                 'first_step_ms': first_ms, 'first_step_of_a_later_batch_ms': new_tree_first_ms,
                                 'steady_step_ms': steady_ms,
                                 'note': 'once per batch of shapes: octree + dual-graph build (host-synchronised) and a first step '
                                         'that builds the per-doctree gather tables; the very first step of a process also packs '
                                         'the weights'},
-            'roofline': roof,
         }
-        if tail:
-            res['roofline_tail'] = res_tail
-        if args.layers:
-            res['layers'] = per_layer(prof)
+        if args.full:
+            res['eager_ms_per_step'] = eager_ms if replay is not None else ms_step
+            res['roofline'] = roof
+            if tail:
+                res['roofline_tail'] = res_tail
+            if args.layers:
+                res['layers'] = per_layer(prof)
+        if dumped is not None:
+            res['outputs'] = dumped
 
     # ---- side measurements (single GPU only; after the contract region) -------------------------------------
-    if world == 1 and rank == 0 and not args.no_extras:
+    if world == 1 and rank == 0 and args.full and not args.no_extras:
         # (before the side runs: they re-pack weights, and the captured graph keeps raw pointers to the current packs)
         # sustained run: keep the GPU busy for >= 3 s so an outside observer (rocm-smi samples) sees the load
         n_sus = max(K, int(3000.0 / max(ms_step, 0.05)) + 1)
@@ -1013,7 +1060,7 @@ def main():
 
         if wl.doc is not None and 6 in wl.doc._csr:
             res['gather'] = gather_microbench(wl.doc, dev)
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if world == 1 and rank == 0 and args.full and not args.no_cpu_baseline:
         if wl.doc is not None:
             res['parity_spot_check'] = parity_spot_check(wl, dev)
             assert res['parity_spot_check']['rel_to_max_vs_oracle'] < 1e-3, res['parity_spot_check']

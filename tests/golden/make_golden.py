@@ -6,6 +6,7 @@ Imports the reference's python files unmodified (via refenv + the `ocnn`
 stand-in) and records inputs / expected outputs.  Only data is written: tensors,
 state_dict key names + shapes, sha256 digests.  No reference source is copied.
 """
+import contextlib
 import os
 import sys
 import types
@@ -247,6 +248,34 @@ def g_dense():
     out['lr_mid'] = {'h': h, 't': t, 'out': lr.forward_as_middle(h, doc, t, None, None)}
     out['split_small'] = split
     save('g_dense', out)
+    # the same three lr runs in float64 (g_dense_f64): their fp32 rounding noise (1e-4 on outputs up to 3.7) moves with
+    # the host's CPU kernels and thread count, so tests/test_oracle_golden.py compares the oracle's float64 run against
+    # these.  Stored rounded to float32 (2e-7 relative, far inside the test's tolerance) to keep the file small.
+    lr = lr.double()
+    with float64_run():
+        f64 = {'lr': {'out': lr(x=x.double(), timesteps=t.double(), x_self_cond=sc.double()),
+                      'out_nosc': lr(x=x.double(), timesteps=t.double())},
+               'lr_mid': {'out': lr.forward_as_middle(h.double(), doc, t.double(), None, None)}}
+    save('g_dense_f64', {k: {n: v.float() for n, v in d.items()} for k, d in f64.items()})
+
+
+@contextlib.contextmanager
+def float64_run():
+    """The reference's float32 spots (GroupNorm32, the `.float()` of the attention softmax, the float32 `arange` of the
+    timestep embedding) follow the input's dtype instead, so that a float64 run is float64 throughout."""
+    from models.networks.diffusion_networks import ldm_diffusion_util as RL
+    norms = [(c, c.forward) for c in (RM.GroupNorm32, RL.GroupNorm32)]
+    to_float, arange = torch.Tensor.float, torch.arange
+    for c, _ in norms:
+        c.forward = torch.nn.GroupNorm.forward
+    torch.Tensor.float = lambda self, *a, **k: self.to(torch.float64)
+    torch.arange = lambda *a, **k: arange(*a, **(dict(k, dtype=torch.float64) if k.get('dtype') == torch.float32 else k))
+    try:
+        yield
+    finally:
+        for c, fw in norms:
+            c.forward = fw
+        torch.Tensor.float, torch.arange = to_float, arange
 
 
 # ---------------------------------------------------------------- G6

@@ -166,6 +166,27 @@ def test_whole_box_cpu_workers_orchestration(monkeypatch):
     assert r['value'] >= max(r['single_process']['value'], 0) * 0.999 or r['value'] == wb['value']
 
 
+def test_bench_dump_outputs_reassembles_lanes_and_caps_its_size(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: x.npy is the whole batch's x (lanes put back at their rows), float32; above the byte cap
+    it is the same seeded sample of whole rows on every call."""
+    import numpy as np
+    import bench
+    x = torch.randn(10, 3, generator=torch.Generator().manual_seed(3))
+    rows = [torch.tensor([0, 1, 2, 3]), torch.tensor([4, 5, 6, 7, 8, 9])]
+    lanes = [types.SimpleNamespace(rows=r, x=x.index_select(0, r)) for r in rows]
+    wl = types.SimpleNamespace(lanes=lanes, x_init=torch.zeros_like(x), x=torch.zeros_like(x))
+    rec = bench.dump_outputs(wl, str(tmp_path / 'a'))
+    got = np.load(tmp_path / 'a' / 'x.npy')
+    assert got.dtype == np.float32 and np.array_equal(got, x.numpy()) and rec['rows_sampled'] is None
+    monkeypatch.setattr(bench, 'DUMP_MAX_BYTES', 4 * 3 * 4)
+    wl = types.SimpleNamespace(lanes=[], x=x.double())
+    rec = bench.dump_outputs(wl, str(tmp_path / 'b'))
+    bench.dump_outputs(wl, str(tmp_path / 'c'))
+    got, again = np.load(tmp_path / 'b' / 'x.npy'), np.load(tmp_path / 'c' / 'x.npy')
+    assert got.shape == (4, 3) and got.dtype == np.float32 and rec['rows_sampled'] == 4 and np.array_equal(got, again)
+    assert all(any(np.array_equal(r, y) for y in x.numpy()) for r in got)
+
+
 def _cpu_octree(depth, fd, seed):
     """A one-element octree on CPU tensors with random splits below the full layer (only the arrays batch_slices /
     merge_octrees touch: keys, children, nnum, nnum_nempty)."""

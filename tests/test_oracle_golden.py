@@ -179,14 +179,19 @@ def test_dense(golden):
     torch.testing.assert_close(OM.attention_block(r['x'], C.fill_state_dict(r['keys']), 4), r['out'], **TOL)
     r = G['resnet']
     torch.testing.assert_close(OM.resnet_block(r['x'], r['emb'], C.fill_state_dict(r['keys'])), r['out'], **TOL)
+    # the whole lr net in float64 on both sides: its fp32 output carries rounding noise of 1e-4 that moves with the
+    # host's CPU kernels and thread count (make_golden.py g_dense)
+    R = {k: {n: v.double() for n, v in d.items()} for k, d in golden('g_dense_f64').items()}
     r = G['lr']
-    sd = C.fill_state_dict(r['keys'])
-    torch.testing.assert_close(OU.lr_forward(sd, C.TINY_LR_CFG, r['x'], r['t'], r['x_self_cond']), r['out'], **TOL)
-    torch.testing.assert_close(OU.lr_forward(sd, C.TINY_LR_CFG, r['x'], r['t']), r['out_nosc'], **TOL)
+    sd = {k: v.double() for k, v in C.fill_state_dict(r['keys']).items()}
+    x, t, sc = r['x'].double(), r['t'].double(), r['x_self_cond'].double()
     oc, doc = small(G['split_small'])
     m = G['lr_mid']
-    torch.testing.assert_close(OU.lr_forward_as_middle(sd, C.TINY_LR_CFG, m['h'], doc, m['t'], None),
-                               m['out'], **TOL)
+    with OM.working_float(torch.float64):
+        torch.testing.assert_close(OU.lr_forward(sd, C.TINY_LR_CFG, x, t, sc), R['lr']['out'], **TOL)
+        torch.testing.assert_close(OU.lr_forward(sd, C.TINY_LR_CFG, x, t), R['lr']['out_nosc'], **TOL)
+        torch.testing.assert_close(OU.lr_forward_as_middle(sd, C.TINY_LR_CFG, m['h'].double(), doc, m['t'].double(), None),
+                                   R['lr_mid']['out'], **TOL)
 
 
 def test_dense_boundary_blocks(golden):

@@ -22,13 +22,13 @@ python tools/pmc_summary.py $OUT/pmc_hr_cond $OUT/pmc_traffic_hr_cond.json hr_co
 python tools/pmc_summary.py $OUT/pmc_feature $OUT/pmc_traffic_feature.json feature >> $OUT/pmc_summary.log 2>&1
 # the bench lines below stamp roofline.traffic from these files (they carry the sha of the kernel sources they were measured on)
 for f in pmc_traffic.json pmc_traffic_hr_cond.json pmc_traffic_feature.json; do cp $OUT/$f profiles/$R/$f; done
-timeout 500 python bench.py --steps 20 --warmup 5 --layers > $OUT/bench_hr.json 2> $OUT/bench_hr.err
+timeout 500 python bench.py --steps 20 --warmup 5 --full --layers > $OUT/bench_hr.json 2> $OUT/bench_hr.err
 for w in lr hr_cond feature; do
-  timeout 500 python bench.py --workload $w --layers > $OUT/bench_$w.json 2> $OUT/bench_$w.err
+  timeout 500 python bench.py --workload $w --full --layers > $OUT/bench_$w.json 2> $OUT/bench_$w.err
 done
 for w in hr lr hr_cond feature; do
   (cd /tmp && timeout -s KILL 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OLDPWD/$OUT/prof_$w -o bench -- \
-    python $OLDPWD/bench.py --workload $w --steps 10 --warmup 3 --no-extras --no-cpu-baseline --eager > $OLDPWD/$OUT/bench_${w}_under_rocprof.json 2> $OLDPWD/$OUT/rocprof_$w.err)
+    python $OLDPWD/bench.py --workload $w --steps 10 --warmup 3 --full --no-extras --no-cpu-baseline --eager > $OLDPWD/$OUT/bench_${w}_under_rocprof.json 2> $OLDPWD/$OUT/rocprof_$w.err)
 done
 (cd /tmp && timeout -s KILL 120 rocprofv3 --kernel-trace --stats --output-format csv -d $OLDPWD/$OUT/prof_gather -o gather -- \
   python $OLDPWD/tools/gather_probe.py > $OLDPWD/$OUT/gather_under_rocprof.json 2> $OLDPWD/$OUT/rocprof_gather.err)
