@@ -667,6 +667,30 @@ int ofx_ddim_eps_update(float* x, const float* eps, const float* coef, float* x0
 int ofx_ddim_x0_update(float* x, const float* x0, const float* noise, const float* coef,
                        int64_t n, void* stream);
 
+/* ------------------------------------------------------------------ marching cubes (csrc/ofx_mesh.hip)
+ * Mesh export of the generate path (export_mesh, octfusion_model_union.py:435-468; create_mesh,
+ * utils/util_dualoctree.py:120-142: skimage marching_cubes + trimesh on the host).  Input: sdf [batch, size, size,
+ * size] fp32, x slowest (what the NeuralMPU sweep writes).  A corner is inside iff v < level (any finite level);
+ * cells (i, j, k) with i, j, k < size - 1; the lattice boundary is not padded.
+ * Vertices: one per lattice edge with exactly one inside endpoint, owned by its lower endpoint a, along +x / +y / +z
+ * to b; index-space p = a + t (b - a), t = (level - v_a) / (v_b - v_a); stored as (p * step + bbmin) * scale
+ * (the reference maps with step = (bbmax - bbmin) / size); ordered by owner linear index, then axis x, y, z.
+ * Triangles: the project's own 256-case table (tools/gen_mc_table.py: ambiguous faces separate their inside corners,
+ * so the mesh is closed away from the boundary), ordered by cell linear index then table order, int32 indices into the
+ * shape's own vertices, (v1 - v0) x (v2 - v0) toward increasing values.  Output is bitwise reproducible (scans, no
+ * atomic appends).  Limits: 2 <= size <= 512 and batch * size^3 * 5 <= INT32_MAX (ofx_mc_ws_bytes returns 0 outside).
+ * ofx_mc_count: counts[b*3 + {0,1,2}] = vertices, triangles, cells with a non-finite corner of shape b (int64).
+ * ofx_mc_emit: after the caller has read the counts back, writes shape b's vertices at verts + 3 * vert_off[b] and its
+ * triangles at faces + 3 * tri_off[b] (offsets: int64 device arrays); ws is the workspace of the count pass (its scans
+ * are read, its id map is written), so the two calls must see the same sdf / level.
+ * ofx_mc_table_host (host memory): tri_table [256 * 16] edge ids, -1 padded, ntri [256].  Corner c = dx*4 + dy*2 + dz,
+ * edge e = axis*4 + k, k = the owner corner's coordinates on the other two axes (x, y, z order, high bit first). */
+size_t ofx_mc_ws_bytes(int batch, int size);
+int ofx_mc_count(const float* sdf, int batch, int size, float level, void* ws, int64_t* counts, void* stream);
+int ofx_mc_emit(const float* sdf, int batch, int size, float level, float step, float bbmin, float scale, void* ws,
+                const int64_t* vert_off, const int64_t* tri_off, float* verts, int32_t* faces, void* stream);
+int ofx_mc_table_host(int8_t* tri_table, uint8_t* ntri);
+
 #ifdef __cplusplus
 }
 #endif

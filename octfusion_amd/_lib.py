@@ -157,6 +157,10 @@ _SIGS = {
     'ofx_linear_small': (c_i, [c_p, c_l, c_i, c_i, c_p, c_l, c_i, c_p, c_p, c_l, c_i, c_i, c_p, c_l, c_p], True),
     'ofx_ddim_eps_update': (c_i, [c_p, c_p, c_p, c_p, c_l, c_p], True),
     'ofx_ddim_x0_update': (c_i, [c_p, c_p, c_p, c_p, c_l, c_p], True),
+    'ofx_mc_ws_bytes': (c_sz, [c_i, c_i], False),
+    'ofx_mc_count': (c_i, [c_p, c_i, c_i, c_f, c_p, c_p, c_p], True),
+    'ofx_mc_emit': (c_i, [c_p, c_i, c_i, c_f, c_f, c_f, c_f, c_p, c_p, c_p, c_p, c_p, c_p], True),
+    'ofx_mc_table_host': (c_i, [c_p, c_p], True),
 }
 
 EXPORTS = sorted(_SIGS)

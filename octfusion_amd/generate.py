@@ -2,8 +2,9 @@
 
 Mirror of the reference's generation loop (train.py:166-185 -> OctFusionModel.sample,
 octfusion_model_union.py:354-401): lr DDIM loop -> octree -> hr DDIM loop (-> feature loop for the 3-stage model) ->
-GraphVAE.decode_code -> NeuralMPU SDF on the resolution^3 lattice (get_sdfs, :425-433).  Marching cubes / mesh export
-(:435-468, skimage + trimesh on the host) is outside the device path.
+GraphVAE.decode_code -> NeuralMPU SDF on the resolution^3 lattice (get_sdfs, :425-433) -> with ``--mesh``, marching
+cubes on the device and ``<out>/<index>.obj`` (export_mesh, :435-468, which runs skimage + trimesh on the host;
+mesh.py lists the differences).
 
 * The sampling nets hold the EMA weights, as the reference's generate does (train.py:181 ``ema=True``;
   ``self.ema_df`` and ``unet_lr=self.ema_df.unet_lr``, octfusion_model_union.py:319,391).
@@ -14,6 +15,7 @@ GraphVAE.decode_code -> NeuralMPU SDF on the resolution^3 lattice (get_sdfs, :42
   once over RCCL (dist.broadcast_module_); nothing is communicated per step.
 
     python -m octfusion_amd.generate --config snet_uncond --shapes 8 --steps 200 [--ckpt df.pth --vae vae.pth]
+    python -m octfusion_amd.generate --config snet_uncond --shapes 8 --mesh --out samples     # + samples/<i>.obj
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \\
         -m octfusion_amd.generate --config snet_cond --shapes 32 --category 2
 """
@@ -73,8 +75,10 @@ def prepare(config, rank, device, ckpt=None, vae_ckpt=None, with_vae=True, allow
 
 
 def generate(net, cfg, n_shapes, rank, world, seed=0, ddim_steps=200, label=None, vae=None, out_dir=None,
-             shapes_per_call=1, use_graph=None, sdf_resolution=None, timings=None):
-    """Yields (result indices, output dict, seconds) for every group of shapes this rank owns."""
+             shapes_per_call=1, use_graph=None, sdf_resolution=None, timings=None, mesh=False, mesh_level=0.0,
+             mesh_scale=1.0):
+    """Yields (result indices, output dict, seconds) for every group of shapes this rank owns.  mesh: also
+    out['meshes'] (needs the VAE and sdf_resolution), written as <out_dir>/<index>.obj."""
     cs = CascadeSampler(net, cfg, vae)
     dev = cs.device
     for idxs in plan(n_shapes, rank, world, shapes_per_call):
@@ -86,7 +90,7 @@ def generate(net, cfg, n_shapes, rank, world, seed=0, ddim_steps=200, label=None
         t0 = time.perf_counter()
         out = cs.sample(len(idxs), ddim_steps=ddim_steps, label=lab, seed=seed, shape_indices=idxs,
                         use_graph=use_graph, sdf_resolution=sdf_resolution if vae is not None else None,
-                        timings=timings)
+                        timings=timings, mesh=mesh, mesh_level=mesh_level, mesh_scale=mesh_scale)
         if dev.type == 'cuda':
             torch.cuda.synchronize()
             from . import ops
@@ -99,7 +103,8 @@ def generate(net, cfg, n_shapes, rank, world, seed=0, ddim_steps=200, label=None
 
 def write_outputs(out_dir, idxs, out, cfg):
     """Per shape: <index>/split_small.pth (+ split_large.pth) in the reference's sample-file format
-    (tools/gen_split.py:50-54), and <index>/sdf.pt when the SDF lattice was computed."""
+    (tools/gen_split.py:50-54), <index>/sdf.pt when the SDF lattice was computed, and <index>.obj (export_mesh's
+    file name, octfusion_model_union.py:466) when the meshes were -- an empty mesh is skipped with a warning."""
     from .octree import octree2split_large, octree2split_small
     small = octree2split_small(out['octree_small'], cfg['full_depth'])
     large = bid = None
@@ -117,6 +122,9 @@ def write_outputs(out_dir, idxs, out, cfg):
             torch.save(large[bid == b].cpu(), os.path.join(d, 'split_large.pth'))
         if 'sdfs' in out:
             torch.save(out['sdfs'][b].cpu(), os.path.join(d, 'sdf.pt'))
+        if 'meshes' in out:
+            from . import mesh
+            mesh.write_obj(os.path.join(out_dir, '%d.obj' % i), *out['meshes'][b])
 
 
 def run(args, rank, local_rank, world, device):
@@ -126,13 +134,22 @@ def run(args, rank, local_rank, world, device):
     label = args.category if cfg.get('num_classes') else None
     if cfg.get('num_classes') and label is None:
         label = 0
+    mesh = getattr(args, 'mesh', False)
+    if mesh:
+        from .mesh import mesh_scale
+    if mesh and (args.no_vae or not args.sdf_resolution):
+        raise ValueError('--mesh needs the VAE and --sdf-resolution')
     per_rank = len(dist.shard_indices(args.shapes, rank, world))
     batch = args.batch or max(1, min(8, per_rank))
     timings = {}
     done = []
+    mesh_counts = {}
+    kw = dict(mesh=True, mesh_level=args.mesh_level, mesh_scale=mesh_scale(args.config)) if mesh else {}
     for idxs, out, dt in generate(net, cfg, args.shapes, rank, world, args.seed, args.steps, label, vae, args.out, batch,
-                                  sdf_resolution=args.sdf_resolution, timings=timings):
+                                  sdf_resolution=args.sdf_resolution, timings=timings, **kw):
         done.append((idxs, dt))
+        for i, (v, f) in zip(idxs, out.get('meshes', ())):
+            mesh_counts[i] = (int(v.shape[0]), int(f.shape[0]))
     total = sum(dt for _, dt in done)
     tmax = dist.max_over_ranks(total, device)
     res = {'config': args.config, 'shapes': args.shapes, 'world': world, 'steps_per_stage': args.steps,
@@ -140,6 +157,9 @@ def run(args, rank, local_rank, world, device):
            'seconds_per_shape': tmax * world / args.shapes if args.shapes else None,
            'shapes_per_s': args.shapes / tmax if tmax > 0 else None, 'rank0_indices': [i for g, _ in done for i in g],
            'rank0_phase_seconds': timings, 'sdf_resolution': args.sdf_resolution if vae is not None else None}
+    if mesh:
+        res['rank0_mesh_vertices'] = [mesh_counts[i][0] for i in res['rank0_indices']]
+        res['rank0_mesh_faces'] = [mesh_counts[i][1] for i in res['rank0_indices']]
     return res
 
 
@@ -158,6 +178,9 @@ def main(argv=None):
                     help='read the checkpoint files with the full unpickler (only for files you trust)')
     ap.add_argument('--sdf-resolution', type=int, default=256)
     ap.add_argument('--out', default=None)
+    ap.add_argument('--mesh', action='store_true',
+                    help='marching cubes on the device; writes <out>/<index>.obj (needs the VAE and --sdf-resolution)')
+    ap.add_argument('--mesh-level', type=float, default=0.0, help='iso level of --mesh (the reference uses 0)')
     args = ap.parse_args(argv)
     rank, local_rank, world = dist.init()
     from . import _lib

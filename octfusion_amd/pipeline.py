@@ -11,7 +11,8 @@ for 3), on device, for a whole batch of independent shapes.
 
     sdf  : NeuralMPU sweep of the decoded field on the resolution^3 lattice in [-sdf_scale, sdf_scale]^3
            (get_sdfs, octfusion_model_union.py:425-433) -- one kernel launch per shape.
-Marching cubes (skimage on the host, octfusion_model_union.py:435-468) is outside the device path.
+    mesh : (opt-in) marching cubes of every lattice on device (mesh.marching_cubes; export_mesh,
+           octfusion_model_union.py:435-468, runs skimage on the host).
 """
 import torch
 
@@ -129,7 +130,8 @@ class CascadeSampler:
             return self._sample_once(*args, **kwargs)
 
     def _sample_once(self, batch_size, ddim_steps=200, label=None, split_small=None, noises=None, sdf_resolution=None,
-                     sdf_scale=0.9, use_graph=None, seed=None, save_index=0, shape_indices=None, timings=None):
+                     sdf_scale=0.9, use_graph=None, seed=None, save_index=0, shape_indices=None, timings=None,
+                     mesh=False, mesh_level=0.0, mesh_scale=1.0):
         """Returns a dict with the per-stage results.  `noises` (optional) = dict of explicit
         init / step noise tensors per stage for reproducible runs.  sdf_resolution (e.g. 256) adds
         out['sdfs'] [B, R, R, R] (needs the VAE).
@@ -139,7 +141,10 @@ class CascadeSampler:
         shape_indices (list of batch_size result indices, needs seed): every shape of the batch gets the noise the
         reference's one-shape-per-call loop would draw for that result index -- a batch of shapes generates what
         batch_size calls with save_index = shape_indices[b] would.
-        timings (optional dict): filled with seconds per phase (host-synchronised: adds a few syncs)."""
+        timings (optional dict): filled with seconds per phase (host-synchronised: adds a few syncs).
+        mesh: when the SDF lattice is computed, also out['meshes'] = per-shape (verts, faces) of its level-`mesh_level`
+        surface in the lattice's [-sdf_scale, sdf_scale]^3 frame times `mesh_scale` (mesh.mesh_scale: the
+        reference's point_scale); one host sync for the count readback."""
         import time as _time
         noises = dict(noises or {})
         out = {}
@@ -222,6 +227,11 @@ class CascadeSampler:
                 out['sdfs'] = mpu.calc_sdf(out['decoded']['neural_mpu'], batch_size, size=sdf_resolution,
                                            bbmin=-sdf_scale, bbmax=sdf_scale)
                 t0 = lap('sdf', t0)
+                if mesh:
+                    from . import mesh as _mesh
+                    out['meshes'] = _mesh.marching_cubes(out['sdfs'], level=mesh_level, bbmin=-sdf_scale,
+                                                         bbmax=sdf_scale, scale=mesh_scale)
+                    t0 = lap('mesh', t0)
         if timings is not None:
             timings.pop('_start', None)
         return out
