@@ -691,6 +691,33 @@ int ofx_mc_emit(const float* sdf, int batch, int size, float level, float step, 
                 const int64_t* vert_off, const int64_t* tri_off, float* verts, int32_t* faces, void* stream);
 int ofx_mc_table_host(int8_t* tri_table, uint8_t* ntri);
 
+/* ------------------------------------------------------------------ evaluation metrics (csrc/ofx_metrics.hip)
+ * The reference's metrics/ package (generate_pointclouds.py:14-37, evaluation_metrics.py:111-201, the CUDA extension
+ * pytorch_structural_losses: nndistance.cu, approxmatch.cu:3-224).  Point clouds are [N, n, 3] fp32, the reference's
+ * layout; tests/metrics_oracle.py restates every function in float64.
+ * ofx_surface_sample: `batch` meshes concatenated -- verts [V, 3] fp32, faces [F, 3] int32 indices into the shape's
+ * own vertices; offs (int64 device) = [vert_off[batch], vert_cnt[batch], face_off[batch], face_cnt[batch]];
+ * total_faces = F; every shape needs >= 1 face and in-range indices (the caller checks).  Per shape: vertex bounding
+ * box, and with normalize the vertices map to (v - box centre) * 2 / max extent (scale_to_unit_cube, padding 0);
+ * triangles are drawn with probability |(B - A) x (C - A)| / sum (fp64 prefix per shape, fixed order), barycentrics
+ * uniform with the u + w > 1 reflection.  The random numbers are r_d = ofx_metrics_hash(seed, id, i, d) for point i
+ * of the shape with id = ids[b] (int64 device array, NULL: b), d = 0 triangle, 1 and 2 barycentrics: the output
+ * out [batch, n, 3] is a pure function of the inputs (bitwise, any launch geometry).  ws: ofx_surface_sample_ws_bytes.
+ * ofx_nn_matrix: d [na, nb] with d[i, j] = mean_p min_q |p - q|^2, p over a[i] ([na, n, 3]), q over b[j] ([nb, m, 3])
+ * -- directed, so Chamfer is d_ab + d_ba^T (the reference's dl.mean + dr.mean); direct differences: a cloud against
+ * itself gives exactly 0.  Any n, m >= 1.
+ * ofx_emd_matrix: e [nx, ny] with e[i, j] = approxmatch cost (x[i] as xyz1, y[j] as xyz2) / n -- emd_approx_cuda of
+ * evaluation_metrics.py:57-62: levels -4^j, j = 7 .. -1, three passes per level, Sum match * |p - q|; not symmetric.
+ * Requires n == m <= OFX_EMD_MAX_POINTS (both clouds live in LDS); anything else is OFX_EINVAL. */
+#define OFX_EMD_MAX_POINTS 2048
+size_t ofx_surface_sample_ws_bytes(int batch, int64_t total_faces);
+int ofx_surface_sample(const float* verts, const int32_t* faces, const int64_t* offs, const int64_t* ids, int batch,
+                       int64_t total_faces, int n, uint64_t seed, int normalize, void* ws, float* out, void* stream);
+int ofx_nn_matrix(const float* a, int64_t na, int n, const float* b, int64_t nb, int m, float* d, void* stream);
+int ofx_emd_matrix(const float* x, int64_t nx, const float* y, int64_t ny, int n, int m, float* e, void* stream);
+/* the sampler's counter hash (host): splitmix64 steps h <- mix(h + 0x9E3779B97F4A7C15 * (x + 1)) over x = id, i, d */
+uint64_t ofx_metrics_hash(uint64_t seed, int64_t shape, int64_t point, int draw);
+
 #ifdef __cplusplus
 }
 #endif

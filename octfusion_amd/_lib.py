@@ -17,6 +17,7 @@ c_i = ctypes.c_int
 c_l = ctypes.c_int64
 c_f = ctypes.c_float
 c_sz = ctypes.c_size_t
+c_u64 = ctypes.c_uint64
 
 
 class OfxTree(ctypes.Structure):
@@ -161,6 +162,11 @@ _SIGS = {
     'ofx_mc_count': (c_i, [c_p, c_i, c_i, c_f, c_p, c_p, c_p], True),
     'ofx_mc_emit': (c_i, [c_p, c_i, c_i, c_f, c_f, c_f, c_f, c_p, c_p, c_p, c_p, c_p, c_p], True),
     'ofx_mc_table_host': (c_i, [c_p, c_p], True),
+    'ofx_surface_sample_ws_bytes': (c_sz, [c_i, c_l], False),
+    'ofx_surface_sample': (c_i, [c_p, c_p, c_p, c_p, c_i, c_l, c_i, c_u64, c_i, c_p, c_p, c_p], True),
+    'ofx_nn_matrix': (c_i, [c_p, c_l, c_i, c_p, c_l, c_i, c_p, c_p], True),
+    'ofx_emd_matrix': (c_i, [c_p, c_l, c_p, c_l, c_i, c_i, c_p, c_p], True),
+    'ofx_metrics_hash': (c_u64, [c_u64, c_l, c_l, c_i], False),
 }
 
 EXPORTS = sorted(_SIGS)

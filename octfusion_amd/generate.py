@@ -16,6 +16,7 @@ mesh.py lists the differences).
 
     python -m octfusion_amd.generate --config snet_uncond --shapes 8 --steps 200 [--ckpt df.pth --vae vae.pth]
     python -m octfusion_amd.generate --config snet_uncond --shapes 8 --mesh --out samples     # + samples/<i>.obj
+    python -m octfusion_amd.generate --config snet_uncond --shapes 8 --mesh --points 2048 --out samples  # + <i>.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \\
         -m octfusion_amd.generate --config snet_cond --shapes 32 --category 2
 """
@@ -24,6 +25,7 @@ import json
 import os
 import time
 
+import numpy as np
 import torch
 
 from . import checkpoint, configs, dist, synthetic
@@ -76,9 +78,11 @@ def prepare(config, rank, device, ckpt=None, vae_ckpt=None, with_vae=True, allow
 
 def generate(net, cfg, n_shapes, rank, world, seed=0, ddim_steps=200, label=None, vae=None, out_dir=None,
              shapes_per_call=1, use_graph=None, sdf_resolution=None, timings=None, mesh=False, mesh_level=0.0,
-             mesh_scale=1.0):
+             mesh_scale=1.0, points=None):
     """Yields (result indices, output dict, seconds) for every group of shapes this rank owns.  mesh: also
-    out['meshes'] (needs the VAE and sdf_resolution), written as <out_dir>/<index>.obj."""
+    out['meshes'] (needs the VAE and sdf_resolution), written as <out_dir>/<index>.obj.  points (needs mesh): also
+    out['points'] = {position in the group: [points, 3] cloud} of every non-empty mesh, sampled on the device after the
+    unit-cube normalisation (metrics.sample_surface keyed by the result index), written as <out_dir>/<index>.npy."""
     cs = CascadeSampler(net, cfg, vae)
     dev = cs.device
     for idxs in plan(n_shapes, rank, world, shapes_per_call):
@@ -96,15 +100,29 @@ def generate(net, cfg, n_shapes, rank, world, seed=0, ddim_steps=200, label=None
             from . import ops
             ops.raise_on_sync_error(dev)         # (the DDIM loops check per stage; this covers the VAE decode)
         dt = time.perf_counter() - t0
+        if points:
+            out['points'] = sample_points(out['meshes'], idxs, points, seed)
         if out_dir is not None:
             write_outputs(out_dir, idxs, out, cfg)
         yield idxs, out, dt
 
 
+def sample_points(meshes, idxs, points, seed):
+    """{position: cloud} of the non-empty meshes of one group, as generate_pointclouds.py samples its OBJ files
+    (metrics/generate_pointclouds.py:33-37), without the OBJ round trip."""
+    from . import metrics
+    keep = [b for b, (_, f) in enumerate(meshes) if f.shape[0] > 0]
+    if not keep:
+        return {}
+    pts = metrics.sample_surface([meshes[b] for b in keep], n=points, seed=seed, ids=[idxs[b] for b in keep])
+    return {b: pts[j] for j, b in enumerate(keep)}
+
+
 def write_outputs(out_dir, idxs, out, cfg):
     """Per shape: <index>/split_small.pth (+ split_large.pth) in the reference's sample-file format
     (tools/gen_split.py:50-54), <index>/sdf.pt when the SDF lattice was computed, and <index>.obj (export_mesh's
-    file name, octfusion_model_union.py:466) when the meshes were -- an empty mesh is skipped with a warning."""
+    file name, octfusion_model_union.py:466) when the meshes were -- an empty mesh is skipped with a warning -- and
+    <index>.npy, its [points, 3] surface samples, when they were."""
     from .octree import octree2split_large, octree2split_small
     small = octree2split_small(out['octree_small'], cfg['full_depth'])
     large = bid = None
@@ -125,6 +143,8 @@ def write_outputs(out_dir, idxs, out, cfg):
         if 'meshes' in out:
             from . import mesh
             mesh.write_obj(os.path.join(out_dir, '%d.obj' % i), *out['meshes'][b])
+        if b in out.get('points', {}):
+            np.save(os.path.join(out_dir, '%d.npy' % i), out['points'][b].cpu().numpy())
 
 
 def run(args, rank, local_rank, world, device):
@@ -139,12 +159,15 @@ def run(args, rank, local_rank, world, device):
         from .mesh import mesh_scale
     if mesh and (args.no_vae or not args.sdf_resolution):
         raise ValueError('--mesh needs the VAE and --sdf-resolution')
+    points = getattr(args, 'points', None)
+    if points is not None and (not mesh or points < 1):
+        raise ValueError('--points needs --mesh and a positive count')
     per_rank = len(dist.shard_indices(args.shapes, rank, world))
     batch = args.batch or max(1, min(8, per_rank))
     timings = {}
     done = []
     mesh_counts = {}
-    kw = dict(mesh=True, mesh_level=args.mesh_level, mesh_scale=mesh_scale(args.config)) if mesh else {}
+    kw = dict(mesh=True, mesh_level=args.mesh_level, mesh_scale=mesh_scale(args.config), points=points) if mesh else {}
     for idxs, out, dt in generate(net, cfg, args.shapes, rank, world, args.seed, args.steps, label, vae, args.out, batch,
                                   sdf_resolution=args.sdf_resolution, timings=timings, **kw):
         done.append((idxs, dt))
@@ -181,6 +204,9 @@ def main(argv=None):
     ap.add_argument('--mesh', action='store_true',
                     help='marching cubes on the device; writes <out>/<index>.obj (needs the VAE and --sdf-resolution)')
     ap.add_argument('--mesh-level', type=float, default=0.0, help='iso level of --mesh (the reference uses 0)')
+    ap.add_argument('--points', type=int, default=None,
+                    help='with --mesh: also write <out>/<index>.npy, that many surface points per shape after the '
+                         'unit-cube normalisation (the input of python -m octfusion_amd.evaluate)')
     args = ap.parse_args(argv)
     rank, local_rank, world = dist.init()
     from . import _lib
