@@ -40,10 +40,8 @@ const char* ofx_status_string(int status);
 /* 0 when a HIP device is present and is gfx950; OFX_ENODEV otherwise. */
 int ofx_device_check(void);
 /* sha256 (16 hex digits) of every source, header and compile flag this library was built from
- * (octfusion_amd/build.py); the Python binding refuses a library whose hash differs from the tree.
- * ofx_build_ablation: 1 for a -DOFX_ABLATION build (timing ablations compiled in), 0 for a product build. */
+ * (octfusion_amd/build.py); the Python binding refuses a library whose hash differs from the tree. */
 const char* ofx_build_hash(void);
-int ofx_build_ablation(void);
 
 /* ------------------------------------------------------------------ fp16x3 range guard (precision 3, the default)
  * Operands travel as fp16 hi + lo pairs (22 significand bits).  What that covers and what it does not:
@@ -473,17 +471,15 @@ int ofx_gn_apply_planes(const float* x, int64_t ldx, int64_t n, int C, const int
  *   left_head int32 [n_left][4] (16-B aligned): every other aux row as (aux row id, first slot in left_src, number of
  *             sources, batch element); always contains the zero row (0, 0, 0, 0); n_own + n_left == n_multi + 1;
  *   left_src  int32: the source rows of the leftover aux rows, flattened (the CSR segment of each, in order).
- * Leftover rows are re-normalised from x by extra blocks interleaved with the main blocks (ofx_set_gn_left_place(1):
- * all behind them, A/B).  mean / rstd from ofx_gn_finalize, or both NULL with (sums, count, groups, eps, count_eps):
- * finalised per block on the fly, as in ofx_gn_apply.  out must not alias x.  Host-side builder:
- * octfusion_amd/dual_octree.py DualOctree.oct_plan. */
+ * Leftover rows are re-normalised from x by extra blocks interleaved with the main blocks.  mean / rstd from
+ * ofx_gn_finalize, or both NULL with (sums, count, groups, eps, count_eps): finalised per block on the fly, as in
+ * ofx_gn_apply.  out must not alias x.  Host-side builder: octfusion_amd/dual_octree.py DualOctree.oct_plan. */
 int ofx_gn_apply_planes_oct(const float* x, int64_t ldx, int64_t n, int C, const int32_t* batch_id, const float* mean,
                             const float* rstd, const double* sums, const float* count, int groups, float eps,
                             float count_eps, const float* w, const float* bias, int act, int mode, void* out,
                             int64_t ldo_bytes, int64_t n_multi, void* aux, const int32_t* oct_ptr,
                             const int32_t* oct_ent, int64_t n_own, int shift, const int32_t* left_head,
                             const int32_t* left_src, int64_t n_left, void* stream);
-int ofx_set_gn_left_place(int at_end);
 /* rows per main block of ofx_gn_apply_planes: the granularity `aux_plan` is built for (the host-side plan builder,
  * octfusion_amd/dual_octree.py aux_plan, asks instead of assuming). */
 int ofx_gn_apply_rows(void);
@@ -499,8 +495,8 @@ int ofx_graphconv_fwd_planes(const void* xp, int64_t ldx_bytes, int cin, int64_t
                              int64_t stats_ld, void* ws, size_t ws_bytes, void* sync /* optional */, size_t sync_bytes,
                              int mode, int aux_ready, void* stream);
 /* 1 (default): persistent launch (whole-tile rounds + a stream-K region) where the shape qualifies; 0: always one tile
- * per block; 2: persistent with pure stream-K (no whole-tile rounds); 3: as 1 with share boundaries snapped towards the
- * tile boundary instead of to the nearest legal cut -- A/B knobs, same values */
+ * per block; 2: persistent with pure stream-K (no whole-tile rounds) -- A/B knob, same values.  Anything else:
+ * OFX_EINVAL. */
 int ofx_set_gconv_persistent(int on);
 /* ofx_gemm_planes (round 6): out[m, :] = A[row_tab[m, 0], :] @ W (+ bias) on the data path of the planes GraphConv
  * (persistent stream-K blocks, LDS-DMA staging, fp16x3 / bf16x3 MFMA; csrc/ofx_gemm3.hip with one "direction") -- the
@@ -517,12 +513,6 @@ int ofx_pack_gemm_planes(const float* W, int64_t sk, int64_t sn, int K, int N, i
 int ofx_gemm_planes(const void* ap, int64_t lda_bytes, int64_t n_a, int64_t M, int K, const int32_t* row_tab,
                     const void* W2, int N, const float* bias, float* out, int64_t ldc, int out_mode, void* ws,
                     size_t ws_bytes, void* sync, size_t sync_bytes, int mode, void* stream);
-/* A/B knob of the dense GEMM (csrc/ofx_gemm.hip): max_n > 0 -> GEMMs with N <= max_n and M >= 65 536 rows use 64-column
- * tiles (three blocks per CU instead of two); 0 = off. */
-int ofx_set_gemm_bn64(int max_n);
-/* A/B knob of the persistent launch's tile order: 1 = every XCD walks one contiguous range of tiles over the whole
- * launch (csrc/ofx_gemm3.hip, Gemm3Args::xcd_contig), 0 = the XCDs interleave inside every whole-tile round. */
-int ofx_set_gconv_xcd_contig(int on);
 /* Plan the persistent launches for at most `cus` compute units (0 = all of the device's; values above the device's
  * count are clamped to it), so that the launches of two lanes on two HIP streams can be resident side by side
  * (octfusion_amd/sampler.py: lanes; tools/two_half_probe.py).  Process-wide; affects launches issued or captured
@@ -533,23 +523,9 @@ int ofx_set_gconv_cus(int cus);
  * whole-tile rounds; out[5 .. 5 + G] = share boundaries of the stream-K region (k-step units, bound(0) = 0,
  * bound(G) = U; every piece between a boundary and a tile edge has >= 8 k-steps).  Returns G, 0 = not eligible. */
 int ofx_gconv3_plan(int64_t n_rows, int cout, int nkt, int wm, int ni, int cus, int32_t* out, int64_t out_len);
-/* scheduling variant of the one-tile-per-block planes kernel: 5 = LDS reads and DMA requests spliced between the
- * MFMAs -- the only one a product build contains (anything else: OFX_EINVAL).  Builds with -DOFX_ABLATION
- * (python -m octfusion_amd.build --ablation) also hold 1 = DMA requests interleaved by sched_group_barrier,
- * 0 = requests before the MFMA group, and 2, 3, 4, 6 = timing ablations with WRONG results (no MFMA / no DMA /
- * no fragment reads / no barrier). */
-int ofx_set_gconv2_variant(int v);
 /* block geometry of the planes kernel: 0 = automatic, 2 = 128 x 128 tiles (4 waves, two blocks per CU),
- * 4 = 256 x 128 tiles (8 waves, one block per CU) -- A/B knob */
+ * 4 = 256 x 128 tiles (8 waves, one block per CU) -- A/B knob.  Anything else: OFX_EINVAL. */
 int ofx_set_gconv2_tile(int wm);
-/* start offset between the two co-resident blocks of a CU (128-row geometry), in shader clocks per k tile of the
- * layer; 0 = start together -- A/B knob */
-int ofx_set_gconv2_stagger(int clocks_per_ktile);
-int ofx_set_gconv2_prefetch(int on);   /* 1 (default): block b pulls the table slice of block b + resident blocks into L2 */
-/* profiling aid (-DOFX_ABLATION builds only; a product build accepts NULL only): when buf != NULL every block of the following ofx_graphconv_fwd_planes launches writes 8 uint64
- * to buf[block*8..]: shader-clock stamps at start / table built / first tile landed / k-loop done / stores drained,
- * then HW_ID.  buf must hold 8 * (tiles of the largest launch) uint64.  NULL switches it off. */
-int ofx_set_gconv2_debug(void* buf);
 
 /* ---------------------------------------------------------------- dense grids
  * The nested dense U-Net (graph_unet_lr.py) in node-row layout: a full octree layer of

@@ -32,7 +32,6 @@ _SIGS = {
     'ofx_status_string': (ctypes.c_char_p, [c_i], False),
     'ofx_device_check': (c_i, [], False),
     'ofx_build_hash': (ctypes.c_char_p, [], False),
-    'ofx_build_ablation': (c_i, [], False),
     'ofx_probe_mfma_sustained': (c_i, [c_i, c_i, c_p, c_p, c_p], True),
     'ofx_scan_ws_bytes': (c_sz, [c_l], False),
     'ofx_scan_i32': (c_i, [c_p, c_p, c_l, c_p, c_p], True),
@@ -116,7 +115,6 @@ _SIGS = {
                                   c_l, c_p, c_p, c_p, c_l, c_p, c_p, c_l, c_p], True),
     'ofx_gn_apply_planes_oct': (c_i, [c_p, c_l, c_l, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_f, c_f, c_p, c_p, c_i, c_i, c_p,
                                       c_l, c_l, c_p, c_p, c_p, c_l, c_i, c_p, c_p, c_l, c_p], True),
-    'ofx_set_gn_left_place': (c_i, [c_i], True),
     'ofx_planes_packed_ktiles': (c_l, [c_i, c_i, c_i], False),
     'ofx_planes_packed_bytes': (c_l, [c_i, c_i, c_i, c_i], False),
     'ofx_pack_weights_planes': (c_i, [c_p, c_l, c_l, c_i, c_i, c_i, c_i, c_p, c_p], True),
@@ -124,18 +122,12 @@ _SIGS = {
                                        c_p, c_p, c_l, c_p, c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_sz, c_p, c_sz, c_i, c_i,
                                        c_p], True),
     'ofx_set_gconv_persistent': (c_i, [c_i], True),
-    'ofx_set_gconv_xcd_contig': (c_i, [c_i], True),
     'ofx_set_gconv_cus': (c_i, [c_i], True),
-    'ofx_set_gemm_bn64': (c_i, [c_i], True),
     'ofx_gemm_planes_packed_bytes': (c_l, [c_i, c_i, c_i], False),
     'ofx_pack_gemm_planes': (c_i, [c_p, c_l, c_l, c_i, c_i, c_i, c_p, c_p], True),
     'ofx_gemm_planes': (c_i, [c_p, c_l, c_l, c_l, c_i, c_p, c_p, c_i, c_p, c_p, c_l, c_i, c_p, c_sz, c_p, c_sz, c_i, c_p], False),
     'ofx_gconv3_plan': (c_i, [c_l, c_i, c_i, c_i, c_i, c_i, c_p, c_l], False),
-    'ofx_set_gconv2_variant': (c_i, [c_i], True),
-    'ofx_set_gconv2_debug': (c_i, [c_p], True),
     'ofx_set_gconv2_tile': (c_i, [c_i], True),
-    'ofx_set_gconv2_stagger': (c_i, [c_i], True),
-    'ofx_set_gconv2_prefetch': (c_i, [c_i], True),
     'ofx_graph_multi_flag': (c_i, [c_p, c_l, c_p, c_p], True),
     'ofx_graph_primary_ext': (c_i, [c_p, c_p, c_l, c_p, c_p, c_p, c_p], True),
     'ofx_graph_primary': (c_i, [c_p, c_p, c_l, c_p, c_p], True),
@@ -203,13 +195,13 @@ def _check_fresh(L):
         return
     from . import build
     try:
-        want = {build.source_hash(), build.source_hash(build.FLAGS + ['-DOFX_ABLATION'])}
+        want = build.source_hash()
     except OSError:
         return                             # sources not shipped: nothing to compare with
     have = L.ofx_build_hash().decode()
-    if have not in want:
+    if have != want:
         raise OfxError('libofx.so is stale: built from sources %s, the tree is %s -- run `python -m octfusion_amd.build`'
-                       % (have, sorted(want)[0] if len(want) == 1 else build.source_hash()))
+                       % (have, want))
 
 
 # bench.py sets PROFILE to a list to time EVERY entry-point call with HIP events on the launching stream (eager runs

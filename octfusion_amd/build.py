@@ -1,6 +1,6 @@
 """Build libofx.so (the C-ABI HIP library) for gfx950 with hipcc, in-tree.
 
-    python -m octfusion_amd.build [--force] [--ablation]
+    python -m octfusion_amd.build [--force]
 
 hipcc cross-compiles without a GPU.  Every translation unit is compiled to its own object (in parallel) and the
 objects are linked into the shared library.  Rebuilds are decided by CONTENT, not by mtime: an object carries the
@@ -8,10 +8,6 @@ sha256 of its source, every header and the flags it was built from (``<obj>.sha`
 of the whole source set (``ofx_build_hash()``), which ``octfusion_amd._lib`` compares with the tree before the
 first call -- a stale ``libofx.so`` (the file is git-ignored and travels with the gpurun snapshot) is refused
 instead of silently run.
-
-``--ablation`` builds a SECOND library, libofx_ablation.so, with -DOFX_ABLATION: the timing-ablation variants of
-the one-tile-per-block planes kernel (wrong results by construction) and the per-block clock-stamp buffer of both
-planes kernels.  The product library never contains them; tools select the profiling build with OFX_LIB=<path>.
 """
 import hashlib
 import os
@@ -47,10 +43,9 @@ def _sha(paths, extra=()):
     return h.hexdigest()
 
 
-def source_hash(flags=None):
+def source_hash():
     """sha256 (first 16 hex digits) of every source, header and compile flag of the library."""
-    flags = FLAGS if flags is None else flags
-    return _sha([os.path.join(CSRC, s) for s in SOURCES] + _headers(), flags)[:16]
+    return _sha([os.path.join(CSRC, s) for s in SOURCES] + _headers(), FLAGS)[:16]
 
 
 def _read(path):
@@ -61,24 +56,18 @@ def _read(path):
         return None
 
 
-ABLATION_LIB = os.path.join(HERE, 'libofx_ablation.so')     # profiling build: OFX_LIB=<this> python tools/...
-
-
-def build(force=False, verbose=False, ablation=False):
+def build(force=False, verbose=False):
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-    # the profiling build has its own objects and file: it never replaces the product library
-    obj_dir, lib = (os.path.join(CSRC, '_obj_ablation'), ABLATION_LIB) if ablation else (OBJ, LIB)
-    os.makedirs(obj_dir, exist_ok=True)
-    flags = FLAGS + (['-DOFX_ABLATION'] if ablation else [])
+    os.makedirs(OBJ, exist_ok=True)
     hdrs = _headers()
     jobs, objs, stamps = [], [], []
     for s in SOURCES:
         src = os.path.join(CSRC, s)
-        obj = os.path.join(obj_dir, s.replace('.hip', '.o'))
-        want = _sha([src] + hdrs, flags)
+        obj = os.path.join(OBJ, s.replace('.hip', '.o'))
+        want = _sha([src] + hdrs, FLAGS)
         objs.append(obj)
         if force or not os.path.exists(obj) or _read(obj + '.sha') != want:
-            jobs.append([hipcc] + flags + ['-c', src, '-o', obj])
+            jobs.append([hipcc] + FLAGS + ['-c', src, '-o', obj])
             stamps.append((obj + '.sha', want))
 
     def run(cmd):
@@ -92,21 +81,20 @@ def build(force=False, verbose=False, ablation=False):
             with open(path, 'w') as f:
                 f.write(want)
     # the hash of the whole source set, compiled into the library
-    tree = source_hash(flags)
-    info_c = os.path.join(obj_dir, 'ofx_buildinfo.cpp')
-    info_o = os.path.join(obj_dir, 'ofx_buildinfo.o')
-    text = ('extern "C" const char* ofx_build_hash() { return "%s"; }\n'
-            'extern "C" int ofx_build_ablation() { return %d; }\n' % (tree, 1 if ablation else 0))
-    relink = bool(jobs) or force or not os.path.exists(lib)
+    tree = source_hash()
+    info_c = os.path.join(OBJ, 'ofx_buildinfo.cpp')
+    info_o = os.path.join(OBJ, 'ofx_buildinfo.o')
+    text = 'extern "C" const char* ofx_build_hash() { return "%s"; }\n' % tree
+    relink = bool(jobs) or force or not os.path.exists(LIB)
     if _read(info_c) != text.strip() or not os.path.exists(info_o):
         with open(info_c, 'w') as f:
             f.write(text)
         run([hipcc, '-O2', '-fPIC', '-c', info_c, '-o', info_o])
         relink = True
     if relink:
-        run([hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', lib] + objs + [info_o])
-    return lib
+        run([hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', LIB] + objs + [info_o])
+    return LIB
 
 
 if __name__ == '__main__':
-    print(build(force='--force' in sys.argv, verbose=True, ablation='--ablation' in sys.argv))
+    print(build(force='--force' in sys.argv, verbose=True))

@@ -27,7 +27,7 @@
 // The epilogue (bias / time-embedding / residual / fused GroupNorm statistics) is shared with ofx_gemm.hip.
 #include "ofx_planes.h"
 
-template <int PREC, int VARIANT, int WM, int NI>
+template <int PREC, int WM, int NI>
 __global__ void __launch_bounds__(512, 2) gconv2_kernel(const Gemm2Args a) {   // (a WM-dependent bound loses the host stub)
   typedef G2Half<PREC, NI> Half;
   typedef G2Cfg<WM, NI> CF;
@@ -52,8 +52,6 @@ __global__ void __launch_bounds__(512, 2) gconv2_kernel(const Gemm2Args a) {   /
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wm = wid >> 1, wn = wid & 1;
   const int l31 = lane & 31, h = lane >> 5;
-  const bool dbg = a.dbg != nullptr;
-  unsigned long long ts0 = 0, ts1 = 0, ts2 = 0, ts3 = 0;
   if (WM == 2 && a.stagger > 0 && blockIdx.x >= 256 && (int)blockIdx.x < a.prefetch) {
     // Two (three with 64-column tiles: 52 KB of LDS each) blocks share a CU and all first-round blocks start together,
     // so their prologues, k-loops and epilogues coincide and nothing overlaps.  Dispatch order observed on gfx950:
@@ -66,7 +64,6 @@ __global__ void __launch_bounds__(512, 2) gconv2_kernel(const Gemm2Args a) {   /
     const unsigned long long t0 = g2_clock();
     while (g2_clock() - t0 < wait) __builtin_amdgcn_s_sleep(32);
   }
-  if (dbg) ts0 = g2_clock();
 
   // ---- neighbour-table slice of this row tile -> LDS, already translated to unsigned 128-B LINE offsets:
   //   tab[r][d < 7] = line offset of source row nbr_ext[m, d] from xlo = min(xp, aux) (rows >= n_src live in `aux`),
@@ -101,14 +98,13 @@ __global__ void __launch_bounds__(512, 2) gconv2_kernel(const Gemm2Args a) {   /
     }
   }
   __syncthreads();
-  if (dbg) ts1 = g2_clock();
 
   // ---- table prefetch for the next round.  The table build above is one exposed HBM miss per block (the 6 MB
   // nbr_ext array is long gone from the caches when the next convolution reads it); block b + S runs on the same XCD
   // one round later (S = co-resident blocks, a multiple of 8), so wave 0 pulls that block's slice (BM * 28 B) into this
   // XCD's L2 now with a DMA load whose LDS destination is never read -- no register, no wait: it is older than every
   // counted load of the pipeline.
-  if (a.prefetch_on && wid == 0) {
+  if (wid == 0) {
     int nb = (int)blockIdx.x + a.prefetch;
     if (nb < ntile) {
       const int q = ntile / 8, r = ntile % 8, xcd = nb % 8, j = nb / 8;
@@ -211,13 +207,6 @@ __global__ void __launch_bounds__(512, 2) gconv2_kernel(const Gemm2Args a) {   /
     }
   // 8 LDS reads: half c of the tile staged at byte offset ob
   auto read_half = [&](int ob, int c, Half& F) {
-    if (VARIANT == 4) {          // ablation: 8 cheap LDS reads (the waits count LDS ops), fragments keep stale registers
-      uint32_t d;
-#pragma unroll
-      for (int u = 0; u < RH; ++u) g2_ds_read32<0>(d, lds0 + G2_TAB);
-      g2_touch(F);
-      return;
-    }
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       g2_ds_read128<0>(F.a[u][0], fa[c][u] + ob);
@@ -252,39 +241,10 @@ __global__ void __launch_bounds__(512, 2) gconv2_kernel(const Gemm2Args a) {   /
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-  auto mfma_half = [&](const Half& F) {
-    if (VARIANT == 2) {          // ablation: keep one MFMA per half so the accumulators stay live
-      acc[0][0] = g2_mfma<PREC>(F.a[0][0], F.b[0][0], acc[0][0]);
-      return;
-    }
-    if (g2_three_term<PREC>()) {
-      // [0] = hi, [1] = lo: small cross terms first, the leading term last
-#pragma unroll
-      for (int i = 0; i < G2_MI; ++i)
-#pragma unroll
-        for (int j = 0; j < G2_NI; ++j) acc[i][j] = g2_mfma<PREC>(F.a[1][i], F.b[0][j], acc[i][j]);
-#pragma unroll
-      for (int i = 0; i < G2_MI; ++i)
-#pragma unroll
-        for (int j = 0; j < G2_NI; ++j) acc[i][j] = g2_mfma<PREC>(F.a[0][i], F.b[1][j], acc[i][j]);
-#pragma unroll
-      for (int i = 0; i < G2_MI; ++i)
-#pragma unroll
-        for (int j = 0; j < G2_NI; ++j) acc[i][j] = g2_mfma<PREC>(F.a[0][i], F.b[0][j], acc[i][j]);
-    } else {
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int i = 0; i < G2_MI; ++i)
-#pragma unroll
-          for (int j = 0; j < G2_NI; ++j) acc[i][j] = g2_mfma<PREC>(F.a[t][i], F.b[t][j], acc[i][j]);
-    }
-  };
-
 #define G2_FENCE() __builtin_amdgcn_sched_barrier(0)
   Half F0, F1;
   G2Idx I;
-  // single MFMA m of a half (same order as mfma_half)
+  // single MFMA m of a half; three-term: [0] = hi, [1] = lo, small cross terms first, the leading term last
   auto mfma_one = [&](const Half& F, auto m_tag) {
     constexpr int m = decltype(m_tag)::value;
     constexpr int per = G2_MI * G2_NI, t = m / per, i = (m / G2_NI) % G2_MI, j = m % G2_NI;
@@ -313,7 +273,7 @@ __global__ void __launch_bounds__(512, 2) gconv2_kernel(const Gemm2Args a) {   /
   constexpr int NMF = (g2_three_term<PREC>() ? 3 : 2) * G2_MI * G2_NI;           // MFMAs per half step
   // MFMAs of half Fc with (a) the LDS reads of the NEXT half set Fr (from stage ob_r, half c_r) and (b) optionally the
   // DMA request of tile T spliced between them, in a pinned order: the reads / requests issue in the shadow of the
-  // matrix pipe instead of in front of it (variant 5; the un-spliced order leaves the pipe idle while a wave issues
+  // matrix pipe instead of in front of it (the un-spliced order leaves the pipe idle while a wave issues
   // its 8-12 LDS reads after every barrier and at every step start)
   auto mfma_spliced = [&](const Half& Fc, bool do_read, int ob_r, int c_r, Half& Fr, auto dma_tag, const Tile& T,
                           int ob_dma) {
@@ -362,7 +322,6 @@ __global__ void __launch_bounds__(512, 2) gconv2_kernel(const Gemm2Args a) {   /
   } else {
     g2_wait_barrier<0>();
   }
-  if (dbg) ts2 = g2_clock();
   read_half(0, 0, F0);
 
   // One k-step.  On entry: F0 = first half of tile `it` (8 reads, possibly still in flight), tile it+1 requested.
@@ -375,20 +334,9 @@ __global__ void __launch_bounds__(512, 2) gconv2_kernel(const Gemm2Args a) {   /
   // the last k-steps; its barrier lets those (and, with 3 stages, the 6 new DMA) stay outstanding.
   G2Epi<G2_MI, G2_NI> P;
   const bool vec4 = g.vec4 != 0;
-  constexpr int MFMAS = (g2_three_term<PREC>() ? 3 : 2) * G2_MI * G2_NI;
-  constexpr int MFMA_PER_ROUND = MFMAS / G2_GLDS_PER_STEP > 0 ? MFMAS / G2_GLDS_PER_STEP : 1;
-  auto interleave_dma = [&]() {
-    // rounds of {MFMAs, address arithmetic, 1 DMA}: the DMA issues ride in the MFMAs' shadow
-#pragma unroll
-    for (int k = 0; k < G2_GLDS_PER_STEP; ++k) {
-      __builtin_amdgcn_sched_group_barrier(0x008, MFMA_PER_ROUND, 0);
-      __builtin_amdgcn_sched_group_barrier(0x006, 6, 0);
-      __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-    }
-  };
   auto step_issue = [&](const Tile& T, auto last_tag) {
     constexpr bool LAST = decltype(last_tag)::value;
-    if constexpr ((VARIANT == 5 || VARIANT == 6) && CF::NBUF == 3) {
+    if constexpr (CF::NBUF == 3) {
       // spliced schedule, 3 stages: table reads | wait F0 (4 younger) | {MFMA F0, read F1, request tile it+2} |
       // barrier | {MFMA F1, read F0 of tile it+1}
       load_idx(T, I);
@@ -399,11 +347,11 @@ __global__ void __launch_bounds__(512, 2) gconv2_kernel(const Gemm2Args a) {   /
         G2_FENCE();
       }
       mfma_spliced(F0, true, ob, 1, F1, std::true_type(), T, obnn);
-      g2_wait_barrier<G2_GLDS_PER_STEP + (LAST ? G2_EPI_LOADS : 0), PREC, VARIANT != 6>(F1);
+      g2_wait_barrier<G2_GLDS_PER_STEP + (LAST ? G2_EPI_LOADS : 0), PREC>(F1);
       G2_FENCE();
       mfma_spliced(F1, true, obn, 0, F0, std::false_type(), T, 0);
       const int t = ob; ob = obn; obn = obnn; obnn = t;
-    } else if constexpr (VARIANT == 5 || VARIANT == 6) {
+    } else {
       // spliced schedule, 2 stages: wait F0 | {MFMA F0, read F1} | barrier | table reads | {MFMA F1, read F0 of tile
       // it+1, request tile it+2 into the buffer tile it just left}
       g2_wait_lgkm<0, PREC>(F0);
@@ -417,56 +365,6 @@ __global__ void __launch_bounds__(512, 2) gconv2_kernel(const Gemm2Args a) {   /
       G2_FENCE();
       load_idx(T, I);
       mfma_spliced(F1, true, obn, 0, F0, std::true_type(), T, ob);
-      const int t = ob; ob = obn; obn = t;
-    } else if constexpr (CF::NBUF == 3) {
-      // 3 stages: tile it+2 is requested in the FIRST half of step it (its buffer was left at step it-1)
-      load_idx(T, I);
-      read_half(ob, 1, F1);
-      g2_wait_lgkm<4 + RH, PREC>(F0);
-      G2_FENCE();
-      if (LAST) {
-        g2_epilogue_request<G2_WM, G2_WN, G2_MI, G2_NI>(g, (const void*)a.W2, P, m0, n0, wm, wn, l31, h);
-        G2_FENCE();
-      }
-      g2_wait_lgkm<RH>(I);
-      if (VARIANT != 3) issue(T, obnn, I);
-      if (VARIANT == 0) {
-        G2_FENCE();
-      }
-      mfma_half(F0);
-      if (VARIANT == 1) interleave_dma();
-      G2_FENCE();
-      g2_wait_barrier<(VARIANT == 3 ? 0 : G2_GLDS_PER_STEP) + (LAST ? G2_EPI_LOADS : 0), PREC>(F1);
-      G2_FENCE();
-      read_half(obn, 0, F0);
-      G2_FENCE();
-      mfma_half(F1);
-      G2_FENCE();
-      const int t = ob; ob = obn; obn = obnn; obnn = t;
-    } else {
-      // 2 stages: tile it+2 goes into the buffer tile `it` leaves at this step's barrier, i.e. it is requested in
-      // the SECOND half of step it and has one k-step to land (the co-resident block covers a late one)
-      read_half(ob, 1, F1);
-      g2_wait_lgkm<RH, PREC>(F0);
-      G2_FENCE();
-      if (LAST) {
-        g2_epilogue_request<G2_WM, G2_WN, G2_MI, G2_NI>(g, (const void*)a.W2, P, m0, n0, wm, wn, l31, h);
-        G2_FENCE();
-      }
-      mfma_half(F0);
-      G2_FENCE();
-      g2_wait_barrier<(LAST ? G2_EPI_LOADS : 0), PREC>(F1);
-      G2_FENCE();
-      load_idx(T, I);
-      read_half(obn, 0, F0);
-      g2_wait_lgkm<RH>(I);
-      if (VARIANT != 3) issue(T, ob, I);
-      if (VARIANT == 0) {
-        G2_FENCE();
-      }
-      mfma_half(F1);
-      if (VARIANT == 1) interleave_dma();
-      G2_FENCE();
       const int t = ob; ob = obn; obn = t;
     }
   };
@@ -490,27 +388,13 @@ __global__ void __launch_bounds__(512, 2) gconv2_kernel(const Gemm2Args a) {   /
     ++it;
   }
   for (; it < nkt; ++it) {                       // last two tiles: nothing left to request
-    if constexpr (VARIANT == 5 || VARIANT == 6) {
-      Tile Tn = {};
-      g2_wait_lgkm<0, PREC>(F0);
-      G2_FENCE();
-      mfma_spliced(F0, true, ob, 1, F1, std::false_type(), Tn, 0);
-      g2_wait_barrier<0, PREC>(F1);
-      G2_FENCE();
-      mfma_spliced(F1, it + 1 < nkt, obn, 0, F0, std::false_type(), Tn, 0);
-    } else {
-    read_half(ob, 1, F1);
-    g2_wait_lgkm<RH, PREC>(F0);
+    Tile Tn = {};
+    g2_wait_lgkm<0, PREC>(F0);
     G2_FENCE();
-    mfma_half(F0);
-    G2_FENCE();
+    mfma_spliced(F0, true, ob, 1, F1, std::false_type(), Tn, 0);
     g2_wait_barrier<0, PREC>(F1);
     G2_FENCE();
-    if (it + 1 < nkt) read_half(obn, 0, F0);
-    G2_FENCE();
-    mfma_half(F1);
-    G2_FENCE();
-    }
+    mfma_spliced(F1, it + 1 < nkt, obn, 0, F0, std::false_type(), Tn, 0);
     if (CF::NBUF == 3) {
       const int t = ob; ob = obn; obn = obnn; obnn = t;
     } else {
@@ -519,19 +403,9 @@ __global__ void __launch_bounds__(512, 2) gconv2_kernel(const Gemm2Args a) {   /
   }
   g2_epilogue_landed(P);
 #undef G2_FENCE
-  if (dbg) ts3 = g2_clock();
 
   if (vec4) g2_epilogue_finish<G2_WM, G2_WN, G2_MI, G2_NI>(g, acc, P, m0, n0, wm, wn, l31, h, osc);
   else epilogue_store_scalar<G2_WM, G2_WN, G2_MI, G2_NI>(g, acc, m0, n0, wm, wn, l31, h, 0);
-  if (dbg) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned long long ts4 = g2_clock();
-    if (threadIdx.x == 0) {
-      unsigned long long* o = a.dbg + (size_t)blockIdx.x * 8;
-      o[0] = ts0; o[1] = ts1; o[2] = ts2; o[3] = ts3; o[4] = ts4;
-      o[5] = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));   // HW_REG_HW_ID
-    }
-  }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -772,54 +646,20 @@ extern "C" int ofx_pack_gemm_planes(const float* W, int64_t sk, int64_t sn, int 
 // ------------------------------------------------------------------------------------------------
 int ofx_launch_stats_reduce(const GemmArgs& g, int wr_rows, hipStream_t st);   // ofx_gemm.hip
 
-// Schedule variants other than 5 (earlier schedules 0 / 1, ablations 2-4 / 6 with WRONG results) and the per-block
-// clock-stamp buffer exist only in -DOFX_ABLATION builds (python -m octfusion_amd.build --ablation); the product
-// library accepts variant 5 and a NULL debug buffer only.
-static int g2_variant = 5;
-extern "C" int ofx_set_gconv2_variant(int v) {
-#ifdef OFX_ABLATION
-  if (v < 0 || v > 6) return OFX_EINVAL;
-#else
-  if (v != 5) return OFX_EINVAL;
-#endif
-  g2_variant = v;
-  return OFX_OK;
-}
-static unsigned long long* g2_debug = nullptr;
-extern "C" int ofx_set_gconv2_debug(void* buf) {
-#ifndef OFX_ABLATION
-  if (buf) return OFX_EINVAL;
-#endif
-  g2_debug = (unsigned long long*)buf;
-  return OFX_OK;
-}
-
-template <int PREC, int VARIANT, int WM, int NI>
+template <int PREC, int WM, int NI>
 static int g2_launch(const Gemm2Args& a, hipStream_t st) {
   static bool attr_set[OFX_MAX_DEVICES] = {};
-  if (!ofx_raise_lds_limit(reinterpret_cast<const void*>(&gconv2_kernel<PREC, VARIANT, WM, NI>), G2Cfg<WM, NI>::LDS, attr_set))
+  if (!ofx_raise_lds_limit(reinterpret_cast<const void*>(&gconv2_kernel<PREC, WM, NI>), G2Cfg<WM, NI>::LDS, attr_set))
     return OFX_ELAUNCH;
-  gconv2_kernel<PREC, VARIANT, WM, NI><<<a.e.ntm * a.e.ntn, G2Cfg<WM, NI>::THREADS, G2Cfg<WM, NI>::LDS, st>>>(a);
+  gconv2_kernel<PREC, WM, NI><<<a.e.ntm * a.e.ntn, G2Cfg<WM, NI>::THREADS, G2Cfg<WM, NI>::LDS, st>>>(a);
   return OFX_OK;
 }
 
 // block geometry: 0 = automatic, 2 = 128-row tiles (two blocks per CU), 4 = 256-row tiles (one block per CU)
 static int g2_wm = 0;
-static int g2_stagger_per_ktile = 1100;     // shader clocks per k tile of the start offset between co-resident blocks
-extern "C" int ofx_set_gconv2_stagger(int clocks_per_ktile) {
-  if (clocks_per_ktile < 0 || clocks_per_ktile > 100000) return OFX_EINVAL;
-  g2_stagger_per_ktile = clocks_per_ktile;
-  return OFX_OK;
-}
-static int g2_prefetch = 1;                 // table prefetch one round ahead (A/B knob)
-static int g2_slots3 = 1;                   // 64-column tiles: assume three co-resident blocks per CU (A/B: bit 1 of `on`)
-extern "C" int ofx_set_gconv2_prefetch(int on) {
-  g2_prefetch = (on & 1) ? 1 : 0;
-  g2_slots3 = (on & 2) ? 0 : 1;             // on = 1: default; on = 3: prefetch with the two-slot assumption
-  return OFX_OK;
-}
+constexpr int G2_STAGGER_PER_KTILE = 1100;  // shader clocks per k tile of the start offset between co-resident blocks
 extern "C" int ofx_set_gconv2_tile(int wm) {
-  if (wm != 0 && wm != 1 && wm != 2 && wm != 4) return OFX_EINVAL;     // 1: the plain width rule (A/B of the automatic choice)
+  if (wm != 0 && wm != 2 && wm != 4) return OFX_EINVAL;
   g2_wm = wm;
   return OFX_OK;
 }
@@ -842,12 +682,10 @@ int ofx_launch_gconv3(Gemm2Args& a, int mode, int wm, int ni, void* ws_tail, siz
                       size_t sync_bytes, hipStream_t st, int nd = 7);
 static int g2_persistent = 1;               // 1 (default): persistent stream-K blocks where the shape qualifies
 void ofx_gconv3_set_hybrid(int on);          // ofx_gemm3.hip
-void ofx_gconv3_set_snap(int near);          // ofx_gemm3.hip
 extern "C" int ofx_set_gconv_persistent(int on) {
-  if (on < 0 || on > 3) return OFX_EINVAL;   // 2: pure stream-K (no whole-tile rounds), 3: round-1 share snapping -- A/B
+  if (on < 0 || on > 2) return OFX_EINVAL;   // 2: pure stream-K (no whole-tile rounds)
   g2_persistent = on ? 1 : 0;
   ofx_gconv3_set_hybrid(on == 2 ? 0 : 1);
-  ofx_gconv3_set_snap(on == 3 ? 0 : 1);
   return OFX_OK;
 }
 
@@ -879,7 +717,6 @@ extern "C" int ofx_graphconv_fwd_planes(const void* xp, int64_t ldx_bytes, int c
   a.xp = (const char*)xp; a.ldx = ldx_bytes; a.aux = (const char*)aux; a.n_src = n_nodes; a.nbr_ext = nbr_ext;
   a.tfp = ntc ? (const char*)tfp : (const char*)xp; a.ldt = ntc ? ldt_bytes : ldx_bytes;
   a.W2 = (const char*)W2;
-  a.dbg = g2_debug;
   a.tpd = (int)(cin / ch); a.nkt_g = 7 * a.tpd; a.nkt = (int)ofx_planes_packed_ktiles(cin, nt, mode);
   GemmArgs& g = a.e;
   g.M = n_nodes; g.N = cout; g.K = g.Kp = (int64_t)a.nkt * ch; g.bias = bias; g.emb = emb; g.lde = lde; g.bid = batch_id;
@@ -906,32 +743,15 @@ extern "C" int ofx_graphconv_fwd_planes(const void* xp, int64_t ldx_bytes, int c
   // (blocks do not run in lock-step rounds, and the second launch pays its own fill and drain) --
   // profiles/r02/gconv2_geometry.txt.
   int rc = OFX_OK;
-#define G2_GO(P_, V_, WM_)                                                                            \
-  (ni == 1 ? (WM_ == 4 ? g2_launch<P_, V_, 4, 1>(a, st) : g2_launch<P_, V_, 2, 1>(a, st))             \
-           : (WM_ == 4 ? g2_launch<P_, V_, 4, 2>(a, st) : g2_launch<P_, V_, 2, 2>(a, st)))
+#define G2_GO(P_, WM_)                                                                        \
+  (ni == 1 ? (WM_ == 4 ? g2_launch<P_, 4, 1>(a, st) : g2_launch<P_, 2, 1>(a, st))             \
+           : (WM_ == 4 ? g2_launch<P_, 4, 2>(a, st) : g2_launch<P_, 2, 2>(a, st)))
   auto launch = [&](int wm, int64_t row0, int64_t rows) -> int {
     a.row0 = row0;
     g.ntm = (int)ofx_cdiv(rows, wm * 64);
-    a.stagger = wm == 2 ? g2_stagger_per_ktile * a.nkt : 0;
-    a.prefetch = wm == 4 ? 256 : (ni == 1 && g2_slots3 ? 768 : 512);      // co-resident blocks (LDS-bound: 1 / 2 / 3 per CU)
-    a.prefetch_on = g2_prefetch;
-#ifdef OFX_ABLATION
-    if (mode == 2) {
-      switch (g2_variant) {
-        case 0: return G2_GO(2, 0, wm);
-        case 2: return G2_GO(2, 2, wm);      // ablations (wrong results): no MFMA / no DMA / no LDS reads
-        case 3: return G2_GO(2, 3, wm);
-        case 4: return G2_GO(2, 4, wm);
-        case 6: return G2_GO(2, 6, wm);      // ablation: spliced schedule without the per-step s_barrier (races)
-        case 1: return G2_GO(2, 1, wm);
-        default: return G2_GO(2, 5, wm);
-      }
-    }
-    if (mode == 3) return G2_GO(3, 5, wm);
-    return g2_variant == 0 ? G2_GO(1, 0, wm) : (g2_variant == 1 ? G2_GO(1, 1, wm) : G2_GO(1, 5, wm));
-#else
-    return mode == 2 ? G2_GO(2, 5, wm) : (mode == 3 ? G2_GO(3, 5, wm) : G2_GO(1, 5, wm));   // (the spliced schedule is the only one in product builds)
-#endif
+    a.stagger = wm == 2 ? G2_STAGGER_PER_KTILE * a.nkt : 0;
+    a.prefetch = wm == 4 ? 256 : (ni == 1 ? 768 : 512);      // co-resident blocks (LDS-bound: 1 / 2 / 3 per CU)
+    return mode == 2 ? G2_GO(2, wm) : (mode == 3 ? G2_GO(3, wm) : G2_GO(1, wm));
   };
   // narrow layers on very long tensors (depth 7 / 8 of the feature net: >= 8 rounds of 256-row tiles) amortise the
   // prologue better with the 256-row geometry too: 2-5 % (tools/gconv2_tile_d8.py)
@@ -943,7 +763,6 @@ extern "C" int ofx_graphconv_fwd_planes(const void* xp, int64_t ldx_bytes, int c
   const bool small_tail = tail4 > 0 && tail4 <= 64 && tiles4 < 1536;
   int wm_auto = (cout <= 128 && tiles4 < 2048) ? 2 : 4;
   if (cout > 128 && small_tail) wm_auto = 2;
-  if (g2_wm == 1) wm_auto = cout <= 128 ? 2 : 4;                       // A/B: the plain width rule
   rc = 1;
   if (g2_persistent && sync) {
     // persistent stream-K launch: no tile quantisation, so the geometry follows the operand traffic alone -- 256-row

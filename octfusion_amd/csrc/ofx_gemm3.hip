@@ -31,9 +31,7 @@
 // {steady..., last steady (requests the epilogue operands), drain A, drain B}.
 #include "ofx_planes.h"
 
-#ifndef G3_NSP
-#define G3_NSP 5               // k-steps the epilogue operand requests of a piece are spread over (A/B: -DG3_NSP=3)
-#endif
+constexpr int G3_NSP = 5;               // k-steps the epilogue operand requests of a piece are spread over
 constexpr int G3_KMIN = G3_NSP + 3;     // shortest piece: one plain step + the request steps + two drain steps
 
 template <int WM, int NI> struct G3Cfg : G2Cfg<WM, NI> {
@@ -44,6 +42,14 @@ template <int WM, int NI> struct G3Cfg : G2Cfg<WM, NI> {
   static constexpr int LDS = RAW + B::BM * 28 + 128;    // 162 944 B (WM 4) / 73 344 B (WM 2) / 56 960 B (WM 2, NI 1)
 };
 
+// `snap`, `xcd_contig`, `rt` and Gemm2Args::dbg are constants now: the switches that set them (round-1 share snapping, one
+// contiguous tile range per XCD, the clock-stamp buffer) were retired with their measurements on record (DESIGN.md 4.1b,
+// 4.5), but the device code that reads them stays as it was.  Measured when the switches went, same machine, alternating
+// runs of the hr step: without the tile remapping +0.60 %, without the `near` argument of g3_bound +0.44 %, without both
+// +0.67 % (gconv3_kernel<3, 4, 2, 7> 249.7 -> 252.7 us) against a run-to-run spread of 0.15 %; without the stamp branches
+// the 128 x 128 instantiations spill to scratch.  Same register counts in every case -- the k-loop of this kernel is that
+// sensitive to where its code lands.  With the fields kept the kernel differs from its previous build in kernel-argument
+// offsets only.
 struct Gemm3Args {
   Gemm2Args b;
   int G;                       // blocks; a multiple of 8
@@ -58,11 +64,12 @@ struct Gemm3Args {
                                // launch believes to be zero, so nothing may wait on these words again until the host
                                // has noticed (ops.raise_on_sync_error), cleared them and switched launch shape
   const char* nbr_lim;         // last 16-B aligned address inside nbr_ext that may be read
-  int snap;                    // 1: share boundaries snapped to the nearest legal cut position, 0: towards the tile boundary (A/B)
+  int snap;                    // always 1: share boundaries snapped to the nearest legal cut position (0 was: towards the tile
+                               // boundary)
   int early;                   // every share spans >= one tile (a tile is cut at most once, and its second piece is
                                // published before the finisher STARTS its own): the finisher starts from that piece
                                // instead of adding it at the end
-  int xcd_contig;              // 1: every XCD walks ONE contiguous range of tiles over the whole launch (its rounds and its
+  int xcd_contig;              // always 0.  1 was: every XCD walks ONE contiguous range of tiles over the whole launch (its rounds and its
                                // part of the region): consecutive rounds of an XCD are neighbours in Morton order, so
                                // the halo rows and the coarse-leaf / aux rows one round pulled into that XCD's L2 are
                                // what the next round gathers again.  0: round r of XCD x = tiles r * G + x * G / 8 ...
@@ -116,7 +123,7 @@ __global__ void __launch_bounds__(512, 2) gconv3_kernel(const Gemm3Args A) {
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wm = wid >> 1, wn = wid & 1;
   const int l31 = lane & 31, h = lane >> 5;
-  const bool dbg = a.dbg != nullptr;
+  const bool dbg = a.dbg != nullptr;      // always false: see the note above Gemm3Args
   unsigned long long ts0 = 0, ts1 = 0;
   int dbg_piece = 0;
   if (dbg) ts0 = g2_clock();
@@ -764,8 +771,6 @@ static int g3_cus() {                  // compute units of the current device (c
 // Bytes of workspace the persistent launch needs behind the statistics partials (0: the shape is not eligible).
 // Launch plan: wm (2 / 4), ni (1 / 2) -> blocks G, units per block.
 struct G3Plan { int G; unsigned q, rem, U; int dp_rounds; size_t part_bytes; };
-static int g3_snap = 1;        // 1: nearest legal cut position; 0: towards the tile boundary (A/B, ofx_set_gconv_persistent(3))
-static int g3_xcd_contig = 0;  // tile order: 1 = one contiguous tile range per XCD (Gemm3Args::xcd_contig), A/B: ofx_set_gconv_xcd_contig
 static int g3_hybrid = 1;      // 1: whole-tile rounds + stream-K region; 0: pure stream-K (A/B, ofx_set_gconv_persistent(2))
 static bool g3_plan(int64_t M, int cout, int nkt, int wm, int ni, G3Plan& p, int cus = 0) {
   if (cus <= 0) cus = g3_cus();
@@ -796,13 +801,11 @@ static bool g3_plan(int64_t M, int cout, int nkt, int wm, int ni, G3Plan& p, int
 }
 
 void ofx_gconv3_set_hybrid(int on) { g3_hybrid = on ? 1 : 0; }
-extern "C" int ofx_set_gconv_xcd_contig(int on) { g3_xcd_contig = on ? 1 : 0; return OFX_OK; }
 extern "C" int ofx_set_gconv_cus(int cus) {
   if (cus < 0 || (cus > 0 && cus < 8)) return OFX_EINVAL;
   g3_cus_override = cus;
   return OFX_OK;
 }
-void ofx_gconv3_set_snap(int near) { g3_snap = near ? 1 : 0; }
 
 // The schedule of a persistent launch, on the host (no device work; `cus` > 0: plan for that many compute units
 // without asking a device): out[0..4] = blocks G, q, rem, region units U, whole-tile rounds; out[5 .. 5 + G] = the
@@ -815,7 +818,7 @@ extern "C" int ofx_gconv3_plan(int64_t n_rows, int cout, int nkt, int wm, int ni
   if (out) {
     if (out_len < 5 + (int64_t)p.G + 1) return 0;
     out[0] = p.G; out[1] = (int32_t)p.q; out[2] = (int32_t)p.rem; out[3] = (int32_t)p.U; out[4] = p.dp_rounds;
-    for (int b = 0; b <= p.G; ++b) out[5 + b] = (int32_t)g3_bound((unsigned)b, p.q, p.rem, (unsigned)nkt, g3_snap != 0);
+    for (int b = 0; b <= p.G; ++b) out[5 + b] = (int32_t)g3_bound((unsigned)b, p.q, p.rem, (unsigned)nkt, true);
   }
   return p.G;
 }
@@ -839,8 +842,8 @@ int ofx_launch_gconv3(Gemm2Args& a, int mode, int wm, int ni, void* ws_tail, siz
   A.G = p.G; A.q = p.q; A.rem = p.rem; A.U = p.U; A.dp_rounds = p.dp_rounds;
   A.part = (float*)ws_tail; A.flags = (unsigned*)sync;
   A.err = (unsigned*)sync + (sync_bytes / sizeof(unsigned) - 1);
-  A.snap = g3_snap;
-  A.xcd_contig = g3_xcd_contig;
+  A.snap = 1;                              // fixed since their A/Bs were retired: see the note above Gemm3Args
+  A.xcd_contig = 0;
   A.rt = p.U / (unsigned)a.nkt;
   // (shares of >= one tile: boundaries are >= nkt apart and snapping only ever moves one ONTO a tile boundary, so a
   // tile has at most one interior cut; its second piece is its block's first work, published ~a tile before the

@@ -562,7 +562,7 @@ extern "C" int ofx_gn_apply_planes(const float* x, int64_t ldx, int64_t n, int C
 // Entries come from the host plan (dual_octree.DualOctree.oct_plan): oct_ptr [n_oct + 1], oct_ent [n_own] (v, mask).
 // Aux rows whose sources do not sit in one octet (17 %: segments of a leaf two levels up -- 7, 10, 13 or 16 sources from
 // several octets -- and sibling leaves of the coarse prefix that straddle a group boundary) are LEFTOVERS: re-normalised
-// from x by extra blocks behind the main blocks, through a host-flattened source list (left_head / left_src).
+// from x by extra blocks among the main blocks, through a host-flattened source list (left_head / left_src).
 // The value summed for an aux row is the value a reader of the stored planes sees (hi + lo, not the unsplit fp32), so
 // the rows equal the stand-alone pre-pass of the planes GraphConv (planes_multi_mean_kernel) bit for bit.
 // Pair modes: the two lanes that hold the eight channels 8 p .. 8 p + 7 of a row (lane parity = parity of the float4 slot:
@@ -609,28 +609,21 @@ __global__ void __launch_bounds__(256) gn_apply_oct_kernel(const float* __restri
                                                            const int32_t* __restrict__ oct_ptr,
                                                            const int2* __restrict__ oct_ent, int64_t n_oct, int shift,
                                                            const int4* __restrict__ lhead,
-                                                           const int32_t* __restrict__ lsrc, int64_t n_left,
-                                                           int left_at_end) {
+                                                           const int32_t* __restrict__ lsrc, int64_t n_left) {
   __shared__ float fin_ms[FIN ? 2 * 2 * 1024 : 1];       // [slot][mean | rstd][C]
   const int CT = C >> 2, RP = 256 / CT;
   const int cl = threadIdx.x % CT, rl = threadIdx.x / CT;
   const int c = cl * 4;
   // leftover blocks: interleaved with the main blocks in dispatch order as in gn_apply_kernel (block i is the a-th
-  // leftover block if the running share i * A / T steps at i), or all behind them (ofx_set_gn_left_place(1), A/B).
+  // leftover block if the running share i * A / T steps at i).
   // What a leftover row costs is the re-read of its 4 ... 16 source rows (depth 8, C = 128: 0.35 GB on top of the main
   // pass's 1.66 GB): interleaved, a leftover block runs about when the main blocks of its sources do and finds part of
-  // them in the memory-side cache -- measured 51.4 us (interleaved) vs 58.2 us (behind) at depth 6, C = 128; equal at
-  // depth 8 (tools/gn_probe_oct_parts.py).
+  // them in the memory-side cache -- measured 51.4 us (interleaved) vs 58.2 us (all behind the main blocks) at depth 6,
+  // C = 128; equal at depth 8 (a later run of the same A/B is recorded in profiles/r06/gn_probe_oct_parts.txt: 52.7 vs
+  // 58.0 us).
   const int64_t gT = gridDim.x;
-  int64_t a_before;
-  bool is_aux;
-  if (left_at_end) {
-    is_aux = (int64_t)blockIdx.x >= gT - aux_blocks;
-    a_before = is_aux ? (int64_t)blockIdx.x - (gT - aux_blocks) : 0;
-  } else {
-    a_before = aux_blocks > 0 ? ((int64_t)blockIdx.x * aux_blocks) / gT : 0;
-    is_aux = aux_blocks > 0 && (((int64_t)blockIdx.x + 1) * aux_blocks) / gT > a_before;
-  }
+  const int64_t a_before = aux_blocks > 0 ? ((int64_t)blockIdx.x * aux_blocks) / gT : 0;
+  const bool is_aux = aux_blocks > 0 && (((int64_t)blockIdx.x + 1) * aux_blocks) / gT > a_before;
   const int64_t aux_id = a_before, main_id = (int64_t)blockIdx.x - a_before;
   const int64_t o = main_id * RP + rl;
   // (256 % (C / 4) != 0 leaves spare lanes; they and the lanes past the last octet / leftover row only attend the barrier)
@@ -791,9 +784,6 @@ __global__ void __launch_bounds__(256) gn_apply_oct_kernel(const float* __restri
   for (int p = p0 + NPRE; p < p1; ++p) entry(oct_ent[p]);
 }
 
-static int g_gn_left_end = 0;              // A/B knob (ofx_set_gn_left_place): 1 = leftover blocks behind the main blocks, 0 = interleaved (default: measured faster)
-extern "C" int ofx_set_gn_left_place(int at_end) { g_gn_left_end = at_end ? 1 : 0; return OFX_OK; }
-
 extern "C" int ofx_gn_apply_planes_oct(const float* x, int64_t ldx, int64_t n, int C, const int32_t* batch_id,
                                        const float* mean, const float* rstd, const double* sums, const float* count,
                                        int groups, float eps, float count_eps, const float* w, const float* bias, int act,
@@ -821,8 +811,7 @@ extern "C" int ofx_gn_apply_planes_oct(const float* x, int64_t ldx, int64_t n, i
   gn_apply_oct_kernel<M_, F_><<<grid, 256, 0, st>>>(x, ldx, n, C, batch_id, mean, rstd, f, w, bias, act, (char*)out,     \
                                                     ldo_bytes, ab, (char*)aux, oct_ptr,                               \
                                                     reinterpret_cast<const int2*>(oct_ent), n_oct, shift,             \
-                                                    reinterpret_cast<const int4*>(left_head), left_src, n_left,       \
-                                                    g_gn_left_end)
+                                                    reinterpret_cast<const int4*>(left_head), left_src, n_left)
     if (mode == 2) { if (mean) GN_GO(2, false); else GN_GO(2, true); }
     else if (mode == 3) { if (mean) GN_GO(3, false); else GN_GO(3, true); }
     else { if (mean) GN_GO(1, false); else GN_GO(1, true); }

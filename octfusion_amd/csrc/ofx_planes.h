@@ -60,11 +60,10 @@ struct Gemm2Args {
   const char* tfp; int64_t ldt;           // node-type slab planes (row pitch bytes) or the activation planes again
   const char* W2;                         // [nkt][N][128 B]
   int tpd, nkt_g, nkt;                    // k tiles per direction, gather tiles (7 * tpd), all tiles
-  unsigned long long* dbg;                // optional [blocks][8] shader-clock stamps (ofx_set_gconv2_debug)
+  unsigned long long* dbg;                // [blocks][16] shader-clock stamps of gconv3_kernel; always NULL (no setter is left)
   int stagger;                            // shader clocks the second block of each CU waits before its first tile (WM 2)
   int prefetch;                           // number of co-resident blocks S (256 x blocks per CU); block b pulls the
                                           // neighbour-table slice of block b + S (same XCD, one round later) into L2
-  int prefetch_on;
   int64_t row0;                           // first output row of this launch (bulk + remainder launches split the rows)
   GemmArgs e;                             // M, N, epilogue operands, tile grid
 };
@@ -138,37 +137,20 @@ __device__ __forceinline__ void g2_wait_lgkm(G2Half<PREC, 1>& F) {
 }
 // wait for all but the newest VM DMA instructions of this wave and for ALL its LDS reads (guarding F), then meet
 // the block.  The memory clobber keeps DMA issues and LDS traffic on their side of the barrier.
-template <int VM, int PREC, bool BAR = true>
+template <int VM, int PREC>
 __device__ __forceinline__ void g2_wait_barrier(G2Half<PREC, 2>& F) {
-  if (!BAR) {                  // ablation only: the waits without the block-wide rendezvous
-    asm volatile("s_waitcnt vmcnt(%8) lgkmcnt(0)"
-                 : "+v"(F.a[0][0]), "+v"(F.a[0][1]), "+v"(F.a[1][0]), "+v"(F.a[1][1]), "+v"(F.b[0][0]), "+v"(F.b[0][1]),
-                   "+v"(F.b[1][0]), "+v"(F.b[1][1])
-                 : "n"(VM)
-                 : "memory");
-    return;
-  }
   asm volatile("s_waitcnt vmcnt(%8) lgkmcnt(0)\n\ts_barrier"
                : "+v"(F.a[0][0]), "+v"(F.a[0][1]), "+v"(F.a[1][0]), "+v"(F.a[1][1]), "+v"(F.b[0][0]), "+v"(F.b[0][1]),
                  "+v"(F.b[1][0]), "+v"(F.b[1][1])
                : "n"(VM)
                : "memory");
 }
-template <int VM, int PREC, bool BAR = true>
+template <int VM, int PREC>
 __device__ __forceinline__ void g2_wait_barrier(G2Half<PREC, 1>& F) {
   asm volatile("s_waitcnt vmcnt(%6) lgkmcnt(0)\n\ts_barrier"
                : "+v"(F.a[0][0]), "+v"(F.a[0][1]), "+v"(F.a[1][0]), "+v"(F.a[1][1]), "+v"(F.b[0][0]), "+v"(F.b[1][0])
                : "n"(VM)
                : "memory");
-}
-template <int PREC>
-__device__ __forceinline__ void g2_touch(G2Half<PREC, 2>& F) {
-  asm volatile("" : "+v"(F.a[0][0]), "+v"(F.a[0][1]), "+v"(F.a[1][0]), "+v"(F.a[1][1]), "+v"(F.b[0][0]), "+v"(F.b[0][1]),
-               "+v"(F.b[1][0]), "+v"(F.b[1][1]));
-}
-template <int PREC>
-__device__ __forceinline__ void g2_touch(G2Half<PREC, 1>& F) {
-  asm volatile("" : "+v"(F.a[0][0]), "+v"(F.a[0][1]), "+v"(F.a[1][0]), "+v"(F.a[1][1]), "+v"(F.b[0][0]), "+v"(F.b[1][0]));
 }
 struct G2Idx { uint32_t v[4]; };
 template <int N>
@@ -182,7 +164,7 @@ __device__ __forceinline__ void g2_wait_barrier() {
 
 // ---- two-phase epilogue.  With ONE block per CU nothing else hides the latency of the epilogue's own loads: the
 // shared epilogue (ofx_gemm_common.h) loads a residual piece, waits for it, stores, 16 times over -- measured at
-// 51 k shader clocks per block against 57 k for the whole 30-step k-loop (tools/gconv2_timeline.py).  Here every
+// 51 k shader clocks per block against 57 k for the whole 30-step k-loop (round-1 clock-stamp timeline).  Here every
 // operand the epilogue needs (residual rows, bias, time-embedding rows, batch ids) is REQUESTED before the last
 // two k-steps and consumed after them.  Same lane -> element mapping as epilogue_store_v4: lane (k = l31 >> 2,
 // q = l31 & 3, h) owns rows q + 4h + 8G + 32i (G < 4, i < MI) of its wave's 32 MI rows, columns 4k..4k+3 of every

@@ -12,7 +12,7 @@ for s in octfusion_amd/csrc/*.hip; do
   pids+=($!)
 done
 for p in "${pids[@]}"; do wait $p; done
-echo "extern \"C\" const char* ofx_build_hash() { return \"variant-$name\"; } extern \"C\" int ofx_build_ablation() { return 0; }" > $obj/ofx_buildinfo.cpp
+echo "extern \"C\" const char* ofx_build_hash() { return \"variant-$name\"; }" > $obj/ofx_buildinfo.cpp
 /opt/rocm/bin/hipcc -O2 -fPIC -c $obj/ofx_buildinfo.cpp -o $obj/ofx_buildinfo.o
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o octfusion_amd/libofx_$name.so $obj/*.o
 echo octfusion_amd/libofx_$name.so

@@ -21,8 +21,7 @@ for W in hr hr_cond feature; do
   done
 done
 for f in pmc_traffic.json pmc_traffic_hr_cond.json pmc_traffic_feature.json generate_probe.json step_trace_hr_b1.json \
-         gn_probe_oct.json gn_probe_oct.txt gn_probe_oct_parts.txt xcd_order_shell6.json xcd_order_shell8.json \
-         gemm_planes_probe.txt narrow_in_probe.txt skip_gemm_probe.txt; do
+         gn_probe_oct.json gn_probe_oct.txt gn_probe_oct_parts.txt gemm_planes_probe.txt narrow_in_probe.txt; do
   [ -s $S/$f ] && cp $S/$f $D/$f
 done
 [ -s gpurun_out/fullwidth_parity.jsonl ] && cp gpurun_out/fullwidth_parity.jsonl $D/fullwidth_parity.jsonl

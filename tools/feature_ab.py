@@ -13,7 +13,7 @@ from octfusion_amd import _lib
 
 name = sys.argv[1] if len(sys.argv) > 1 else 'feature'
 knob = sys.argv[2] if len(sys.argv) > 2 else 'ofx_set_gconv2_tile'
-va, vb = (int(sys.argv[3]), int(sys.argv[4])) if len(sys.argv) > 4 else (1, 0)
+va, vb = (int(sys.argv[3]), int(sys.argv[4])) if len(sys.argv) > 4 else (2, 0)
 dev = torch.device('cuda:0')
 torch.set_grad_enabled(False)
 wl = bench.Workload(name, bench.WORKLOADS[name]['batch'] if 'batch' in bench.WORKLOADS[name] else 8, dev, 0)

@@ -2,7 +2,7 @@
 # Round evidence run on the GPU box (one box, one call): PMC passes over the planes-kernel probe (hr, hr_cond and feature
 # layer sets), bench lines of the four BASELINE workloads, rocprofv3 kernel stats of ALL FOUR bench commands (+ the gather
 # microbenchmark row), step traces, native-node listing, the generate probe, and the round's A/B probes (GroupNorm octet
-# launch, XCD tile order, dense GEMM on the planes path, input convolution, 1x1 skip tile width).
+# launch, dense GEMM on the planes path, input convolution).
 # Everything lands under gpurun_out/final/; tools/collect_profiles.sh copies what is to be judged into profiles/r06/.
 set -u
 cd "${GRAFT_REPO_ROOT:-.}"
@@ -42,11 +42,8 @@ timeout 600 python tools/generate_probe.py --out $OUT/generate_probe.json > $OUT
 # ---- the round's A/B probes
 timeout 300 python tools/gn_probe_oct.py both --out $OUT/gn_probe_oct.json > $OUT/gn_probe_oct.txt 2>&1
 timeout 300 python tools/gn_probe_oct_parts.py both > $OUT/gn_probe_oct_parts.txt 2>&1
-timeout 300 python tools/gconv3_xcd_probe.py shell6 --json $OUT/xcd_order_shell6.json > $OUT/xcd_order_shell6.txt 2>&1
-timeout 300 python tools/gconv3_xcd_probe.py shell8 --json $OUT/xcd_order_shell8.json > $OUT/xcd_order_shell8.txt 2>&1
 timeout 300 python tools/gemm_planes_probe.py > $OUT/gemm_planes_probe.txt 2>&1
 timeout 300 python tools/narrow_in_probe.py > $OUT/narrow_in_probe.txt 2>&1
-timeout 300 python tools/skip_gemm_probe.py > $OUT/skip_gemm_probe.txt 2>&1
 python - <<'PY'
 import json
 for w in ('hr', 'lr', 'hr_cond', 'feature'):

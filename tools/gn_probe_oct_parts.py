@@ -46,13 +46,8 @@ def run(doc, shapes, tag):
                  n_own, ptr(aux), sbase + 4 * o_ptr, sbase + 4 * o_ent, n_own, shift, ptr(zero_left), sbase + 4 * o_src, 1, stream())
         t_seq = timeit(go2) if n_own else float('nan')
         print('   owned rows with sequential ids: %.1f us' % t_seq)
-        call('ofx_set_gn_left_place', 0)
-        t_left_i = timeit(lambda: go(ptr(zptr), 0, base + 4 * o_head, n_left))
-        t_all_i = timeit(lambda: go(base + 4 * o_ptr, n_own, base + 4 * o_head, n_left))
-        call('ofx_set_gn_left_place', 1)
-        fo = lambda **kw: None
-        print('%s d%d C=%d N=%d: main only %.1f us (%.2f TB/s) | + owned (%d) %.1f | main + leftovers (%d) %.1f | all %.1f || interleaved: main + leftovers %.1f | all %.1f' % (
-            tag, d, C, N, t_main, 8e-6 * N * C / t_main, n_own, t_own, n_left, t_left, t_all, t_left_i, t_all_i), flush=True)
+        print('%s d%d C=%d N=%d: main only %.1f us (%.2f TB/s) | + owned (%d) %.1f | main + leftovers (%d) %.1f | all %.1f' % (
+            tag, d, C, N, t_main, 8e-6 * N * C / t_main, n_own, t_own, n_left, t_left, t_all), flush=True)
 oc = split2octree_small(synthetic.shell6_split(8).to(dev), 6, 4)
 if which in ('hr', 'both'):
     run(DualOctree(oc), [(6, 128), (6, 256), (6, 384), (5, 256), (5, 768)], 'shell6x8')
