@@ -59,6 +59,15 @@ const char* ofx_build_hash(void);
  *    (exact count, diagnostics).  The caller checks finiteness of a stage's result and the word once per batch of
  *    launches (octfusion_amd.ops.raise_on_range_error) and re-runs in bf16x3 (precision 0: fp32's exponent range,
  *    16 significand bits).
+ *  - GRADIENTS ride in the activation slot of every data-gradient contraction (ofx_graphconv_bwd_data,
+ *    ofx_gridconv_bwd_data, ofx_gemm_f32 on dy) and are NOT O(1): the gradient of an MSE over 1e5..1e7 elements starts
+ *    at 2 / numel, where the 3e-8 floor above is the whole value (measured: DESIGN.md section 4.3).  These entry
+ *    points therefore expect dy normalised by a power of two so that max|dy| lies in [2^7, 2^8) -- 2^8 of headroom
+ *    below 65504 for the weighted segment sums of the reverse graph -- and the caller multiplies dx by the inverse:
+ *    octfusion_amd.ops.grad_pow2 (device-side amax -> frexp -> ldexp, no host synchronisation), applied by
+ *    ops.graphconv_backward, backward.gridconv_backward, ops.linear_backward and ops.gemm_grad.  Exact both ways, so
+ *    dx stays homogeneous in dy.  The weight-gradient contractions (ofx_*_bwd_weight, ofx_gemm_tn_f32) run on bf16
+ *    pairs or exact fp32 (fp32's exponent range) and take dy as it is.
  * ofx_set_range_words: device pointer to >= 4 zeroed uint32 on the CURRENT device (NULL: counting off).  Sticky. */
 int ofx_set_range_words(uint32_t* words);
 
@@ -205,8 +214,11 @@ int ofx_graph_primary_ext_w(const int32_t* seg_ptr, const int32_t* col, const fl
  *   cout, nt = 0).  nbr_rev / nbr_ext_rev / multi_seg come from the _w table builders above; aux: scratch of
  *   (n_multi + 1) * ldy floats.
  * _bwd_weight: dWp [Kp, cout] = col_data^T @ dy in the PACKED k order of ofx_pack_weights (k = dir*cin + c,
- *   zero rows up to pad32(7*cin), then the 7*nt node-type rows), exact fp32 MFMA, deterministic slice-ordered
- *   reduction.  ws holds the partial sums (and, for cin % 32 != 0, col-row chunks). */
+ *   zero rows up to pad32(7*cin), then the 7*nt node-type rows), bf16 hi + lo pair MFMA (three products, ~16
+ *   significand bits; exact fp32 MFMA under ofx_set_precision(1)), deterministic slice-ordered reduction.  ws holds
+ *   the partial sums (and, for cin % 32 != 0, col-row chunks of >= 32 rows: a ws too small for either is
+ *   OFX_EINVAL with nothing launched; a small ws only lowers the slice count / chunk size, never the result's
+ *   accuracy class).  ofx_gridconv_bwd_weight likewise. */
 int ofx_graphconv_bwd_data(const float* dy, int64_t ldy, int cout, int64_t n_nodes, const int32_t* nbr_rev,
                            const int32_t* rev_ptr, const int32_t* rev_row, const float* rev_w,
                            const int32_t* nbr_ext_rev, const int32_t* multi_seg, int64_t n_multi, float* aux,
@@ -225,7 +237,8 @@ int ofx_gn_backward(const float* x, int64_t ldx, const float* dy, int64_t ldy, i
                     const float* mean, const float* rstd, const float* w, const float* bias, int act, double* sums,
                     float* coef, float* dx, int64_t lddx, float* dgamma, float* dbeta, void* stream);
 /* out [K, N] = P^T Q for row-major P [rows, K], Q [rows, N] (weight gradients of the dense layers: dW = x^T dy).
- * K, N multiples of 4; exact fp32 MFMA, slice-ordered (deterministic) reduction of the partials held in ws. */
+ * K, N multiples of 4; bf16 hi + lo pair MFMA (exact fp32 MFMA under ofx_set_precision(1)), slice-ordered
+ * (deterministic) reduction of the partials held in ws (at least K * N floats, else OFX_EINVAL). */
 int ofx_gemm_tn_f32(const float* P, int64_t ldp, const float* Q, int64_t ldq, int64_t rows, int64_t K, int64_t N,
                     float* out, void* ws, size_t ws_bytes, void* stream);
 /* Reverse tables for any tap table (the dense layers' 27-tap grid tables): nbr [n_out, ndir], valid sources in

@@ -76,12 +76,15 @@ def gridconv_backward(conv, x, dy, gs, need_dx=True):
         rv = gs.cache.rev(mode, d_out)
         wt = ops.PackedConv3d().get(conv.weight.detach().transpose(0, 1).contiguous())
         dx = torch.empty(n_in, cin, dtype=torch.float32, device=dev)
-        fast = cout % 32 == 0 and ldy % 4 == 0
-        aux = torch.empty((rv['V'] + 1) * ldy, dtype=torch.float32, device=dev) if fast else None
-        call('ofx_gridconv_bwd_data', ptr(dy), ldy, cout, n_out, n_in, ptr(rv['nbr']), ptr(rv['rev_ptr']),
+        dys, inv = ops.grad_pow2(dy)                       # dy rides in the un-scaled activation slot: normalise it
+        lds = dys.stride(0)
+        fast = cout % 32 == 0 and lds % 4 == 0
+        aux = torch.empty((rv['V'] + 1) * lds, dtype=torch.float32, device=dev) if fast else None
+        call('ofx_gridconv_bwd_data', ptr(dys), lds, cout, n_out, n_in, ptr(rv['nbr']), ptr(rv['rev_ptr']),
              ptr(rv['rev_row']), ptr(rv['rev_w']), ptr(rv['nbr_ext']) if fast else None,
              ptr(rv['multi_seg']) if fast else None, rv['V'] if fast else 0, ptr(aux), ptr(wt.t), cin, ptr(dx), cin,
              ptr(ws), ws.numel(), stream())
+        dx.mul_(inv)
     Kp = lib().ofx_conv3d_packed_k(cin)
     dwp = torch.empty(Kp, cout, dtype=torch.float32, device=dev)
     fast = cin % 32 == 0 and ldx % 4 == 0
@@ -383,7 +386,7 @@ def _unpool_bwd(up, x, dout, doctree, d, G, prefix):
         ops.rows_copy(x, xa, n_ne, smap=a_rows)
         w2 = up.weights.view(C, 8 * C)
         G.add(prefix + 'weights', ops.gemm_tn(xa, dU).view_as(up.weights))
-        dxa = ops.gemm(dU, ops.PackedWeight().get(w2, 'nk'))             # dU @ w2^T
+        dxa = ops.gemm_grad(dU, ops.PackedWeight().get(w2, 'nk'))        # dU @ w2^T
         ops.rows_copy(dxa, dx, n_ne, dmap=a_rows)                        # those rows receive nothing else
     else:
         G.add(prefix + 'weights', torch.zeros_like(up.weights))

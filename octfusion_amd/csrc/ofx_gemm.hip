@@ -1431,7 +1431,10 @@ extern "C" int ofx_graphconv_bwd_data(const float* dy, int64_t ldy, int cout, in
 // Backward of GraphConv with respect to its weights: dW[k, o] = sum_r col_data[r, k] * dy[r, o] -- a "TN"
 // contraction whose reduction index is the node row r of BOTH operands.  The 32x32x2 fp32 MFMA takes one
 // element per lane for each operand (A: row = lane & 31 at k = lane >> 5), so tiles that are contiguous along
-// k-of-W / o (= along the lanes) feed it straight from LDS without any transpose, in exact fp32.
+// k-of-W / o (= along the lanes) feed it straight from LDS without any transpose, in exact fp32 -- that is the
+// ofx_set_precision(1) mode.  In every other mode (the default included) the contraction runs on bf16 hi + lo pairs
+// (three v_mfma_f32_32x32x16_bf16 per product, ~16 significand bits, fp32's exponent range: gradients of any
+// magnitude are safe here), see tn_gemm_kernel.
 // col_data rows are gathered on the fly exactly like the forward pass (extended table + aux rows from the same
 // multi-neighbour pre-pass, node-type slab for the trailing columns); layers the branch-free gather cannot take
 // go through col_rows_kernel chunks with DENSE_P = true.
@@ -1636,6 +1639,7 @@ extern "C" int ofx_graphconv_bwd_weight(const float* x, int64_t ldx, int cin, in
                                                                                n_multi, aux, ldx, nullptr);
     int slices = (int)ofx_cdiv(1024, tiles);
     if (slices > 256) slices = 256;
+    if (slices > (int)ofx_cdiv(n_nodes, 32)) slices = (int)ofx_cdiv(n_nodes, 32);   // (as its two siblings below)
     while (slices > 1 && (size_t)slices * total * sizeof(float) > ws_bytes) --slices;
     if ((size_t)slices * total * sizeof(float) > ws_bytes) return OFX_EINVAL;
     a.x = x; a.ldx = ldx; a.cin = cin; a.ndir = 7; a.nbr_ext = nbr_ext; a.aux = aux; a.n_src = n_nodes;
@@ -1677,7 +1681,8 @@ extern "C" int ofx_graphconv_bwd_weight(const float* x, int64_t ldx, int cin, in
 }
 
 // out[K, N] = P^T @ Q for row-major P [rows, K], Q [rows, N] (the weight gradient of every Linear / Conv1x1 /
-// pool / unpool layer: dW = x^T dy).  Exact fp32 MFMA, deterministic.  ws: slices * K * N floats of partials.
+// pool / unpool layer: dW = x^T dy).  bf16-pair MFMA (exact fp32 MFMA under ofx_set_precision(1)), deterministic
+// (partials reduced in slice order).  ws: slices * K * N floats of partials.
 // Backward of the 27-tap grid convolution (nn.Conv3d 3^3 of the dense lr net in node-row layout).
 // _bwd_data: dx [n_in, cin] = the same gather-GEMM over the reverse tap table (summing segments: stride-2 and
 //   upsample+conv taps fan in) with W^T per tap (WpT = ofx_pack_conv3d of weight.transpose(0, 1)).

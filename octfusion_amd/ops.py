@@ -871,10 +871,36 @@ def gemm_tn(p, q):
     return out
 
 
+GRAD_TOP_EXP = 8      # a normalised gradient has its largest |value| in [2^7, 2^8)
+
+
+def grad_pow2(dy):
+    """(dy * 2^s, 2^-s as a device scalar) with s chosen on the device so that max |dy * 2^s| lies in [2^7, 2^8).
+
+    Every data-gradient contraction puts dy in the ACTIVATION slot of the fp16-pair GEMMs, which is not scaled
+    (include/ofx.h, "fp16x3 range guard"): below ~2^-3 the lo half is an fp16 denormal and the operand keeps an
+    absolute error of ~3e-8, which is the whole value for the gradients of an MSE over 1e5..1e7 elements.  The
+    normalisation is an exact power of two both ways (results stay homogeneous in dy), costs no host synchronisation
+    (aminmax -> frexp -> ldexp on the device) and leaves 2^8 of headroom for the weighted segment sums of the reverse
+    graph (at most 8 finer neighbours per face / 8 children per stride-2 tap) before fp16's 65504.
+    An all-zero dy keeps s = 8; a non-finite maximum gives a clamped, meaningless s and the non-finite values go
+    through to the result as before."""
+    lo, hi = torch.aminmax(dy) if dy.numel() else (dy.new_zeros(()), dy.new_zeros(()))
+    _, e = torch.frexp(torch.maximum(-lo, hi))            # max |dy| = m * 2^e, m in [0.5, 1); 0 -> e = 0
+    s = (GRAD_TOP_EXP - e).clamp(-100, 100)
+    return torch.ldexp(dy, s), torch.ldexp(torch.ones_like(hi), -s)
+
+
+def gemm_grad(dy, pw):
+    """dy @ W for a gradient dy (any magnitude): ops.gemm on the power-of-two normalised dy, scaled back."""
+    dys, inv = grad_pow2(dy)
+    return gemm(dys, pw).mul_(inv)
+
+
 def linear_backward(x, dy, weight, need_dx=True):
     """y = x @ weight^T + bias (nn.Linear / Conv1x1, weight [out, in]): returns (dx, dW [out, in], dbias [out])."""
     dW = gemm_tn(dy, x)
-    dx = gemm(dy, PackedWeight().get(weight, 'kn')) if need_dx else None        # dy [n, out] @ W [out, in]
+    dx = gemm_grad(dy, PackedWeight().get(weight, 'kn')) if need_dx else None   # dy [n, out] @ W [out, in]
     return dx, dW, dy.sum(0)
 
 
@@ -897,11 +923,14 @@ def graphconv_backward(x, dy, doctree, d, weights, n_node_type, need_dx=True, ne
         wt = weights.detach().view(7, cin + nt, cout)[:, :cin, :].permute(0, 2, 1).reshape(7 * cout, cin).contiguous()
         pwt = PackedWeight().get(wt, 'graphconv', cout, 0)
         dx = torch.empty(N, cin, dtype=torch.float32, device=x.device)
-        fast = cout % 32 == 0 and ldy % 4 == 0
-        aux = torch.empty((rv['V'] + 1) * ldy, dtype=torch.float32, device=x.device) if fast else None
-        call('ofx_graphconv_bwd_data', ptr(dy), ldy, cout, N, ptr(rv['nbr']), ptr(rv['rev_ptr']), ptr(rv['rev_row']),
+        dys, inv = grad_pow2(dy)                           # dy rides in the un-scaled activation slot: normalise it
+        lds = dys.stride(0)
+        fast = cout % 32 == 0 and lds % 4 == 0
+        aux = torch.empty((rv['V'] + 1) * lds, dtype=torch.float32, device=x.device) if fast else None
+        call('ofx_graphconv_bwd_data', ptr(dys), lds, cout, N, ptr(rv['nbr']), ptr(rv['rev_ptr']), ptr(rv['rev_row']),
              ptr(rv['rev_w']), ptr(rv['nbr_ext']) if fast else None, ptr(rv['multi_seg']) if fast else None,
              rv['V'] if fast else 0, ptr(aux), ptr(pwt.t), pwt.Kp, cin, ptr(dx), cin, ptr(ws), ws.numel(), stream())
+        dx.mul_(inv)
     if need_dw:
         L = _lib.lib()
         Kp = L.ofx_graphconv_packed_k(cin, nt)
