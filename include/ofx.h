@@ -680,6 +680,52 @@ int ofx_mc_emit(const float* sdf, int batch, int size, float level, float step, 
                 const int64_t* vert_off, const int64_t* tri_off, float* verts, int32_t* faces, void* stream);
 int ofx_mc_table_host(int8_t* tri_table, uint8_t* ntri);
 
+/* ------------------------------------------------------------------ mesh components (csrc/ofx_mesh_cc.hip)
+ * export_mesh's clean=True (models/octfusion_model_union.py:459-467; the same code in octfusion_model_vae.py:242-250):
+ * trimesh.split(only_watertight=False), keep the component whose bounding box has the largest side.
+ * tests/cc_oracle.py restates every function below with numpy / scipy.
+ * Input: a batch mesh in the layout ofx_mc_emit writes -- verts [V, 3] fp32, faces [F, 3] int32 local to each shape,
+ * vert_off / tri_off int64 [batch + 1] (ascending, from 0 to total_verts / total_faces).  Limits: batch >= 1 and
+ * 1 <= total_verts, total_faces <= INT32_MAX (ofx_mesh_cc_ws_bytes returns 0 outside).  `ws` is one workspace of
+ * ofx_mesh_cc_ws_bytes bytes shared by the calls on one mesh, in the order label, then table (+ stats) or select
+ * (+ extract); `status` is two int32 the caller reads back with its counts: status[0] != 0 a capped union-find loop
+ * gave up (the results are not to be used), status[1] != 0 a face index outside its shape's [0, n_verts) (bit 0) or
+ * inconsistent offsets (bit 1) -- then no later pass touches the mesh.
+ * Two vertices are connected when a face uses both.  label[v] = the lowest vertex id of v's component within its shape
+ * (a vertex that no face uses: itself); components with at least one face are numbered 0 .. K-1 by ascending label.
+ * Everything is a function of the mesh alone (integer min / max atomics and scans, no atomic appends): bitwise
+ * reproducible.
+ * ofx_mesh_cc_label (:459, the split): range check, union-find (hook the larger root under the smaller, path halving,
+ *   capped loops), flatten in a launch of its own.  label: int32 [V].
+ * ofx_mesh_cc_table (:459): comp_of_vert int32 [V] (optional; -1 for an unused vertex) and comp_off int32
+ *   [batch + 1], the offsets of the shapes' components in the dense numbering (comp_off[batch] = all components).
+ * ofx_mesh_cc_stats (:461, the extents' inputs): after _table and the caller's readback of comp_off[batch] = n_comp,
+ *   table int32 [n_comp, 8]: columns 0-2 / 3-5 the fp32 bits of the exact bounding-box min / max, 6 the vertex
+ *   count, 7 the face count.
+ * ofx_mesh_cc_select (:461-465): per shape the component with the largest max-axis extent (fp32 subtraction of the
+ *   stored coordinates), a tie to the lowest label; winner_label int32 [batch] (-1: no face); keep_counts int64
+ *   [3 * batch]: kept vertices, kept faces, components before cleaning.  Needs neither _table nor _stats.
+ * ofx_mesh_cc_extract (:466): after the caller has read keep_counts back, writes shape b's kept vertices at out_verts +
+ *   3 * new_vert_off[b] and kept faces, renumbered, at out_faces + 3 * new_tri_off[b], both in their original order; ws
+ *   is the workspace ofx_mesh_cc_select left. */
+size_t ofx_mesh_cc_ws_bytes(int64_t total_verts, int64_t total_faces, int batch);
+int ofx_mesh_cc_label(const int32_t* faces, const int64_t* vert_off, const int64_t* tri_off, int batch,
+                      int64_t total_verts, int64_t total_faces, int32_t* label, void* ws, int32_t* status,
+                      void* stream);
+int ofx_mesh_cc_table(const int32_t* faces, const int32_t* label, const int64_t* vert_off, const int64_t* tri_off,
+                      int batch, int64_t total_verts, int64_t total_faces, int32_t* comp_of_vert, int32_t* comp_off,
+                      void* ws, const int32_t* status, void* stream);
+int ofx_mesh_cc_stats(const float* verts, const int32_t* faces, const int32_t* label, const int64_t* vert_off,
+                      const int64_t* tri_off, int batch, int64_t total_verts, int64_t total_faces, int64_t n_comp,
+                      int32_t* table, void* ws, const int32_t* status, void* stream);
+int ofx_mesh_cc_select(const float* verts, const int32_t* faces, const int32_t* label, const int64_t* vert_off,
+                       const int64_t* tri_off, int batch, int64_t total_verts, int64_t total_faces,
+                       int32_t* winner_label, int64_t* keep_counts, void* ws, const int32_t* status, void* stream);
+int ofx_mesh_cc_extract(const float* verts, const int32_t* faces, const int64_t* vert_off, const int64_t* tri_off,
+                        int batch, int64_t total_verts, int64_t total_faces, const int64_t* new_vert_off,
+                        const int64_t* new_tri_off, float* out_verts, int32_t* out_faces, void* ws,
+                        const int32_t* status, void* stream);
+
 /* ------------------------------------------------------------------ evaluation metrics (csrc/ofx_metrics.hip)
  * The reference's metrics/ package (generate_pointclouds.py:14-37, evaluation_metrics.py:111-201, the CUDA extension
  * pytorch_structural_losses: nndistance.cu, approxmatch.cu:3-224).  Point clouds are [N, n, 3] fp32, the reference's

@@ -3,7 +3,8 @@
 The reference runs metrics/generate_pointclouds.py (meshes -> 2048-point .npy clouds), then metrics/cov_mmd.py and
 metrics/1-NNA.py on .pth tensors.  This driver does all three (octfusion_amd.metrics):
 
-    python -m octfusion_amd.evaluate --samples PATH --refs PATH [--points 2048] [--seed 0] [--no-emd] [--out metrics.json]
+    python -m octfusion_amd.evaluate --samples PATH --refs PATH [--points 2048] [--seed 0] [--no-emd] [--clean]
+                                     [--out metrics.json]
 
 A PATH is a directory of .obj files (sampled on the device after the unit-cube normalisation, --points per shape),
 a directory of .npy [n, 3] clouds (what generate_pointclouds.py and ``generate --points`` write), or a .pt / .pth
@@ -20,8 +21,10 @@ import torch
 SAMPLE_GROUP = 64            # meshes per sample_surface call
 
 
-def load_clouds(path, points=2048, seed=0):
-    """[N, n, 3] float32 (device for OBJ input, host otherwise) from a PATH as described in the module docstring."""
+def load_clouds(path, points=2048, seed=0, clean=False):
+    """[N, n, 3] float32 (device for OBJ input, host otherwise) from a PATH as described in the module docstring.
+    clean: keep only the largest component of every mesh read from .obj (mesh.largest_component) before sampling;
+    no effect on .npy / .pt input."""
     from . import mesh, metrics
     if os.path.isdir(path):
         names = sorted(os.listdir(path))
@@ -36,6 +39,8 @@ def load_clouds(path, points=2048, seed=0):
                 if len(fc) == 0:
                     raise ValueError('%s has no faces' % os.path.join(path, f))
                 meshes.append((v, fc))
+            if clean:
+                meshes = clean_meshes(meshes)
             parts = [metrics.sample_surface(meshes[g:g + SAMPLE_GROUP], n=points, seed=seed,
                                             ids=list(range(g, g + len(meshes[g:g + SAMPLE_GROUP]))))
                      for g in range(0, len(meshes), SAMPLE_GROUP)]
@@ -54,6 +59,17 @@ def load_clouds(path, points=2048, seed=0):
     raise ValueError('%s: not a directory, .pt or .pth file' % path)
 
 
+def clean_meshes(meshes):
+    """The largest component of every host (verts, faces) pair, as device tensors (mesh.largest_component)."""
+    from . import mesh, metrics
+    dev = metrics._device()
+    out = []
+    for g in range(0, len(meshes), SAMPLE_GROUP):
+        out += mesh.largest_component([(torch.from_numpy(v).to(dev), torch.from_numpy(f).to(dev))
+                                       for v, f in meshes[g:g + SAMPLE_GROUP]])
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--samples', required=True)
@@ -61,12 +77,15 @@ def main(argv=None):
     ap.add_argument('--points', type=int, default=2048, help='points per shape sampled from .obj input')
     ap.add_argument('--seed', type=int, default=0, help='seed of the surface sampler')
     ap.add_argument('--no-emd', action='store_true', help='Chamfer only')
+    ap.add_argument('--clean', action='store_true',
+                    help='keep only the largest connected component of every mesh loaded from .obj before sampling '
+                         '(the reference\'s clean=True); no effect on .npy, .pt or .pth input')
     ap.add_argument('--out', default=None)
     args = ap.parse_args(argv)
     from . import _lib, metrics
     _lib.require_device()
-    sample = load_clouds(args.samples, args.points, args.seed)
-    ref = load_clouds(args.refs, args.points, args.seed)
+    sample = load_clouds(args.samples, args.points, args.seed, args.clean)
+    ref = load_clouds(args.refs, args.points, args.seed, args.clean)
     res = metrics.evaluate(sample, ref, emd=not args.no_emd)
     line = json.dumps(res)
     print(line)

@@ -17,6 +17,7 @@ mesh.py lists the differences).
     python -m octfusion_amd.generate --config snet_uncond --shapes 8 --steps 200 [--ckpt df.pth --vae vae.pth]
     python -m octfusion_amd.generate --config snet_uncond --shapes 8 --mesh --out samples     # + samples/<i>.obj
     python -m octfusion_amd.generate --config snet_uncond --shapes 8 --mesh --points 2048 --out samples  # + <i>.npy
+    python -m octfusion_amd.generate --config snet_uncond --shapes 8 --mesh --clean --out samples   # largest component
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \\
         -m octfusion_amd.generate --config snet_cond --shapes 32 --category 2
 """
@@ -78,11 +79,15 @@ def prepare(config, rank, device, ckpt=None, vae_ckpt=None, with_vae=True, allow
 
 def generate(net, cfg, n_shapes, rank, world, seed=0, ddim_steps=200, label=None, vae=None, out_dir=None,
              shapes_per_call=1, use_graph=None, sdf_resolution=None, timings=None, mesh=False, mesh_level=0.0,
-             mesh_scale=1.0, points=None):
+             mesh_scale=1.0, points=None, mesh_clean=False):
     """Yields (result indices, output dict, seconds) for every group of shapes this rank owns.  mesh: also
     out['meshes'] (needs the VAE and sdf_resolution), written as <out_dir>/<index>.obj.  points (needs mesh): also
     out['points'] = {position in the group: [points, 3] cloud} of every non-empty mesh, sampled on the device after the
-    unit-cube normalisation (metrics.sample_surface keyed by the result index), written as <out_dir>/<index>.npy."""
+    unit-cube normalisation (metrics.sample_surface keyed by the result index), written as <out_dir>/<index>.npy.
+    mesh_clean (needs mesh): the meshes, files and clouds are those of each shape's largest component, and
+    out['mesh_components'] holds the component counts before cleaning."""
+    if mesh_clean and not mesh:
+        raise ValueError('mesh_clean needs mesh')
     cs = CascadeSampler(net, cfg, vae)
     dev = cs.device
     for idxs in plan(n_shapes, rank, world, shapes_per_call):
@@ -94,7 +99,8 @@ def generate(net, cfg, n_shapes, rank, world, seed=0, ddim_steps=200, label=None
         t0 = time.perf_counter()
         out = cs.sample(len(idxs), ddim_steps=ddim_steps, label=lab, seed=seed, shape_indices=idxs,
                         use_graph=use_graph, sdf_resolution=sdf_resolution if vae is not None else None,
-                        timings=timings, mesh=mesh, mesh_level=mesh_level, mesh_scale=mesh_scale)
+                        timings=timings, mesh=mesh, mesh_level=mesh_level, mesh_scale=mesh_scale,
+                        **({'mesh_clean': True} if mesh_clean else {}))
         if dev.type == 'cuda':
             torch.cuda.synchronize()
             from . import ops
@@ -162,17 +168,25 @@ def run(args, rank, local_rank, world, device):
     points = getattr(args, 'points', None)
     if points is not None and (not mesh or points < 1):
         raise ValueError('--points needs --mesh and a positive count')
+    clean = getattr(args, 'clean', False)
+    if clean and not mesh:
+        raise ValueError('--clean needs --mesh')
     per_rank = len(dist.shard_indices(args.shapes, rank, world))
     batch = args.batch or max(1, min(8, per_rank))
     timings = {}
     done = []
     mesh_counts = {}
+    mesh_comps = {}
     kw = dict(mesh=True, mesh_level=args.mesh_level, mesh_scale=mesh_scale(args.config), points=points) if mesh else {}
+    if clean:
+        kw['mesh_clean'] = True
     for idxs, out, dt in generate(net, cfg, args.shapes, rank, world, args.seed, args.steps, label, vae, args.out, batch,
                                   sdf_resolution=args.sdf_resolution, timings=timings, **kw):
         done.append((idxs, dt))
         for i, (v, f) in zip(idxs, out.get('meshes', ())):
             mesh_counts[i] = (int(v.shape[0]), int(f.shape[0]))
+        for i, k in zip(idxs, out.get('mesh_components', ())):
+            mesh_comps[i] = int(k)
     total = sum(dt for _, dt in done)
     tmax = dist.max_over_ranks(total, device)
     res = {'config': args.config, 'shapes': args.shapes, 'world': world, 'steps_per_stage': args.steps,
@@ -183,6 +197,8 @@ def run(args, rank, local_rank, world, device):
     if mesh:
         res['rank0_mesh_vertices'] = [mesh_counts[i][0] for i in res['rank0_indices']]
         res['rank0_mesh_faces'] = [mesh_counts[i][1] for i in res['rank0_indices']]
+    if clean:
+        res['rank0_mesh_components'] = [mesh_comps[i] for i in res['rank0_indices']]
     return res
 
 
@@ -207,7 +223,13 @@ def main(argv=None):
     ap.add_argument('--points', type=int, default=None,
                     help='with --mesh: also write <out>/<index>.npy, that many surface points per shape after the '
                          'unit-cube normalisation (the input of python -m octfusion_amd.evaluate)')
+    ap.add_argument('--clean', action='store_true',
+                    help='with --mesh: keep only the largest connected component of every mesh (the reference\'s '
+                         'export_mesh clean=True); the .obj, the --points cloud and the vertex / face counts are the '
+                         'cleaned mesh\'s, and the result line gains rank0_mesh_components (counts before cleaning)')
     args = ap.parse_args(argv)
+    if args.clean and not args.mesh:
+        raise ValueError('--clean needs --mesh')
     rank, local_rank, world = dist.init()
     from . import _lib
     _lib.require_device()

@@ -8,7 +8,10 @@ Differences from the reference:
   * the triangulation table is the project's own (tools/gen_mc_table.py): same vertices as skimage (one per crossing
     lattice edge, linear interpolation), but in ambiguous cells the topology may differ from the Lewiner tables;
   * an empty shape is skipped with a warning -- the reference returns at the first empty shape and drops the rest of
-    the batch (octfusion_model_union.py:453-455).
+    the batch (octfusion_model_union.py:453-455);
+  * clean=True (keep the component whose bounding box has the largest side, :459-467) runs on the device
+    (csrc/ofx_mesh_cc.hip: components, largest_component): connectivity is by shared vertex where trimesh uses edges
+    shared by exactly two faces, extents are fp32, a tie goes to the lowest vertex id.
 """
 import os
 import warnings
@@ -37,7 +40,7 @@ def _max_batch(size):
     return max(1, (2 ** 31 - 1) // (MAX_TRI_PER_CELL * size ** 3))
 
 
-def marching_cubes(sdfs, level=0.0, bbmin=-0.9, bbmax=0.9, scale=1.0):
+def marching_cubes(sdfs, level=0.0, bbmin=-0.9, bbmax=0.9, scale=1.0, clean=False, stats=None):
     """Meshes of a batch of SDF lattices ``sdfs`` [B, R, R, R] (fp32 on the device, x slowest; what
     ``mpu.calc_sdf`` and the pipeline produce).  Returns a list of B ``(verts [V, 3] fp32, faces [F, 3] int32)``
     device tensors: vertices in ``(index * (bbmax - bbmin) / R + bbmin) * scale`` coordinates, faces 0-based into
@@ -46,7 +49,12 @@ def marching_cubes(sdfs, level=0.0, bbmin=-0.9, bbmax=0.9, scale=1.0):
 
     Makes ONE host synchronisation: the per-shape counts are read back between the count and the emit pass (once
     per group of ``(2^31 - 1) // (5 R^3)`` shapes -- 25 at R = 256).  Raises ValueError naming the shape if a cell
-    of it has a non-finite corner, and OfxError without a GPU (there is no CPU path)."""
+    of it has a non-finite corner, and OfxError without a GPU (there is no CPU path).
+
+    clean=True keeps only each shape's largest component (the reference's export_mesh clean=True; what
+    ``largest_component`` returns), straight from the batch buffers the mesher wrote, for one more host
+    synchronisation per group (the kept counts).  stats (optional dict, with clean): ``stats['components']`` becomes
+    the list of the shapes' component counts before cleaning."""
     _lib.require_device()
     if sdfs.dim() != 4 or not (sdfs.shape[1] == sdfs.shape[2] == sdfs.shape[3]):
         raise ValueError('marching_cubes: sdfs must be [B, R, R, R], got %s' % (tuple(sdfs.shape),))
@@ -60,13 +68,16 @@ def marching_cubes(sdfs, level=0.0, bbmin=-0.9, bbmax=0.9, scale=1.0):
     sdfs = sdfs.contiguous()
     step = (float(bbmax) - float(bbmin)) / R
     out = []
+    comps = [] if clean else None
     g = _max_batch(R)
     for b0 in range(0, B, g):
-        out += _group(sdfs[b0:b0 + g], b0, R, float(level), step, float(bbmin), float(scale))
+        out += _group(sdfs[b0:b0 + g], b0, R, float(level), step, float(bbmin), float(scale), comps)
+    if clean and stats is not None:
+        stats['components'] = comps
     return out
 
 
-def _group(sdf, b0, R, level, step, bbmin, scale):
+def _group(sdf, b0, R, level, step, bbmin, scale, comps=None):
     B = int(sdf.shape[0])
     dev = sdf.device
     st = _lib.stream()
@@ -87,7 +98,190 @@ def _group(sdf, b0, R, level, step, bbmin, scale):
     offs = torch.stack([voff, toff]).to(dev)
     _lib.call('ofx_mc_emit', _lib.ptr(sdf), B, R, level, step, bbmin, scale, _lib.ptr(ws), _lib.ptr(offs[0]),
               _lib.ptr(offs[1]), _lib.ptr(verts), _lib.ptr(faces), st)
+    if comps is not None:                              # clean=True: the batch buffers go on as they are
+        return _clean(verts, faces, nv.tolist(), nt.tolist(), comps)
     return [(verts[int(voff[b]):int(voff[b] + nv[b])], faces[int(toff[b]):int(toff[b] + nt[b])]) for b in range(B)]
+
+
+# ---- components (csrc/ofx_mesh_cc.hip): export_mesh's clean=True, octfusion_model_union.py:459-467 ------------------
+_INT32_MAX = 2 ** 31 - 1
+_last_cc_status = (0, 0)
+
+
+def last_cc_status():
+    """(loop cap tripped, bad face index) words of the latest component call, as read back with its counts."""
+    return _last_cc_status
+
+
+def _check_meshes(meshes, who):
+    meshes = list(meshes)
+    for k, m in enumerate(meshes):
+        if not (isinstance(m, (tuple, list)) and len(m) == 2 and torch.is_tensor(m[0]) and torch.is_tensor(m[1])):
+            raise ValueError('%s: shape %d is not a (verts, faces) pair of tensors' % (who, k))
+        v, f = m
+        if v.device.type != 'cuda' or f.device.type != 'cuda' or v.device != f.device:
+            raise ValueError('%s: shape %d is not on the device' % (who, k))
+        if v.dtype != torch.float32 or f.dtype != torch.int32:
+            raise ValueError('%s: shape %d must have float32 vertices and int32 faces' % (who, k))
+        if v.dim() != 2 or v.shape[1] != 3 or f.dim() != 2 or f.shape[1] != 3:
+            raise ValueError('%s: shape %d must be verts [V, 3], faces [F, 3]' % (who, k))
+        if v.shape[0] > _INT32_MAX or f.shape[0] > _INT32_MAX:
+            raise ValueError('%s: shape %d has more than 2^31 - 1 vertices or faces' % (who, k))
+    return meshes
+
+
+def _mesh_groups(meshes):
+    """Runs of consecutive meshes whose vertices and whose faces each fit one int32 scan (as _max_batch does)."""
+    groups, cur, V, F = [], [], 0, 0
+    for k, (v, f) in enumerate(meshes):
+        if cur and (V + v.shape[0] > _INT32_MAX or F + f.shape[0] > _INT32_MAX):
+            groups.append(cur)
+            cur, V, F = [], 0, 0
+        cur.append(k)
+        V += int(v.shape[0])
+        F += int(f.shape[0])
+    if cur:
+        groups.append(cur)
+    return groups
+
+
+def _cat(meshes):
+    if len(meshes) == 1:
+        return meshes[0][0].contiguous(), meshes[0][1].contiguous()
+    return torch.cat([v for v, _ in meshes]).contiguous(), torch.cat([f for _, f in meshes]).contiguous()
+
+
+def _label(verts, faces, nv, nf):
+    """Label one batch mesh: (offsets [2, B + 1] on the device, label, workspace, status words)."""
+    B, V, F = len(nv), sum(nv), sum(nf)
+    dev = faces.device
+    nbytes = _lib.lib().ofx_mesh_cc_ws_bytes(V, F, B)
+    if nbytes == 0:
+        raise ValueError('mesh components: %d vertices, %d faces outside [1, 2^31 - 1]' % (V, F))
+    offs = torch.from_numpy(np.stack([np.concatenate([[0], np.cumsum(nv)]),
+                                      np.concatenate([[0], np.cumsum(nf)])]).astype(np.int64)).to(dev)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    label = torch.empty(V, dtype=torch.int32, device=dev)
+    status = torch.empty(2, dtype=torch.int32, device=dev)
+    _lib.call('ofx_mesh_cc_label', _lib.ptr(faces), _lib.ptr(offs[0]), _lib.ptr(offs[1]), B, V, F, _lib.ptr(label),
+              _lib.ptr(ws), _lib.ptr(status), _lib.stream())
+    return offs, label, ws, status
+
+
+def _read_back(counts, status, who):
+    """The one host synchronisation of a pass: its counts and the two status words."""
+    global _last_cc_status
+    host = torch.cat([counts.flatten().to(torch.int64), status.to(torch.int64)]).cpu()
+    cap, bad = int(host[-2]), int(host[-1])
+    _last_cc_status = (cap, bad)
+    if bad:
+        raise ValueError('%s: %s' % (who, 'a face index lies outside [0, V) of its shape' if bad & 1
+                                     else 'inconsistent offsets'))
+    if cap:
+        raise _lib.OfxError('%s: a union-find loop hit its cap (status %d)' % (who, cap))
+    return host[:-2]
+
+
+def _clean(verts, faces, nv, nf, comps=None, who='largest_component'):
+    """Largest component of every shape of one batch mesh (nv / nf: per-shape counts on the host)."""
+    B, V, F = len(nv), sum(nv), sum(nf)
+    if F == 0 or V == 0:
+        if comps is not None:
+            comps += [0] * B
+        return [(verts[:0], faces[:0]) for _ in range(B)]
+    dev = faces.device
+    st = _lib.stream()
+    offs, label, ws, status = _label(verts, faces, nv, nf)
+    winner = torch.empty(B, dtype=torch.int32, device=dev)
+    keep = torch.empty(3 * B, dtype=torch.int64, device=dev)
+    _lib.call('ofx_mesh_cc_select', _lib.ptr(verts), _lib.ptr(faces), _lib.ptr(label), _lib.ptr(offs[0]),
+              _lib.ptr(offs[1]), B, V, F, _lib.ptr(winner), _lib.ptr(keep), _lib.ptr(ws), _lib.ptr(status), st)
+    c = _read_back(keep, status, who).view(3, B)       # the host sync
+    kv, kf = c[0], c[1]
+    if comps is not None:
+        comps += c[2].tolist()
+    nvo = torch.cumsum(kv, 0) - kv
+    nfo = torch.cumsum(kf, 0) - kf
+    out_v = torch.empty(max(int(kv.sum()), 1), 3, dtype=torch.float32, device=dev)
+    out_f = torch.empty(max(int(kf.sum()), 1), 3, dtype=torch.int32, device=dev)
+    new = torch.stack([nvo, nfo]).to(dev)
+    _lib.call('ofx_mesh_cc_extract', _lib.ptr(verts), _lib.ptr(faces), _lib.ptr(offs[0]), _lib.ptr(offs[1]), B, V, F,
+              _lib.ptr(new[0]), _lib.ptr(new[1]), _lib.ptr(out_v), _lib.ptr(out_f), _lib.ptr(ws), _lib.ptr(status), st)
+    return [(out_v[int(nvo[b]):int(nvo[b] + kv[b])], out_f[int(nfo[b]):int(nfo[b] + kf[b])]) for b in range(B)]
+
+
+def largest_component(meshes, stats=None):
+    """The reference's ``export_mesh(clean=True)`` rule (octfusion_model_union.py:459-467) on the device: of every
+    mesh of ``meshes`` -- ``(verts [V, 3] fp32, faces [F, 3] int32)`` device tensors, as ``marching_cubes`` returns
+    them -- keep the connected component whose bounding box has the largest side.  Two vertices are connected when
+    a face uses both; a tie goes to the component with the lowest vertex id.  Returns a list of pairs of the same
+    types: kept vertices and faces in their original order, indices renumbered, bitwise reproducible.  A mesh with
+    one component comes back with equal contents (minus vertices no face uses); a mesh without faces comes back
+    empty.  One host synchronisation per group (the kept counts).  stats (optional dict): ``stats['components']``
+    becomes the component counts before cleaning.  Raises ValueError for a wrong dtype or device or a face index
+    outside ``[0, V)`` (checked on the device before anything follows an index), OfxError without a GPU."""
+    _lib.require_device()
+    meshes = _check_meshes(meshes, 'largest_component')
+    out, comps = [], []
+    for grp in _mesh_groups(meshes):
+        part = [meshes[k] for k in grp]
+        v, f = _cat(part)
+        out += _clean(v, f, [int(m[0].shape[0]) for m in part], [int(m[1].shape[0]) for m in part], comps)
+    if stats is not None:
+        stats['components'] = comps
+    return out
+
+
+def components(meshes):
+    """The component table of every mesh of ``meshes`` (device ``(verts, faces)`` pairs as for
+    ``largest_component``): one dict per shape with ``comp_of_vert`` int32 [V] (-1 for a vertex no face uses),
+    ``comp_of_face`` int32 [F], ``bbox_min`` / ``bbox_max`` fp32 [K, 3] (exact minima / maxima of the stored
+    coordinates) and ``n_verts`` / ``n_faces`` int64 [K].  Components are numbered by their lowest vertex id; only
+    components with a face are listed (an empty mesh: K = 0).  One host synchronisation per group (the component
+    counts).  Same errors as ``largest_component``."""
+    _lib.require_device()
+    meshes = _check_meshes(meshes, 'components')
+    out = []
+    for grp in _mesh_groups(meshes):
+        part = [meshes[k] for k in grp]
+        nv = [int(m[0].shape[0]) for m in part]
+        nf = [int(m[1].shape[0]) for m in part]
+        out += _components(*_cat(part), nv, nf)
+    return out
+
+
+def _components(verts, faces, nv, nf):
+    B, V, F = len(nv), sum(nv), sum(nf)
+    dev = faces.device
+    if F == 0 or V == 0:
+        return [dict(comp_of_vert=torch.full((n,), -1, dtype=torch.int32, device=dev),
+                     comp_of_face=torch.empty(0, dtype=torch.int32, device=dev),
+                     bbox_min=torch.empty(0, 3, device=dev), bbox_max=torch.empty(0, 3, device=dev),
+                     n_verts=torch.empty(0, dtype=torch.int64, device=dev),
+                     n_faces=torch.empty(0, dtype=torch.int64, device=dev)) for n in nv]
+    st = _lib.stream()
+    offs, label, ws, status = _label(verts, faces, nv, nf)
+    cov = torch.empty(V, dtype=torch.int32, device=dev)
+    coff = torch.empty(B + 1, dtype=torch.int32, device=dev)
+    _lib.call('ofx_mesh_cc_table', _lib.ptr(faces), _lib.ptr(label), _lib.ptr(offs[0]), _lib.ptr(offs[1]), B, V, F,
+              _lib.ptr(cov), _lib.ptr(coff), _lib.ptr(ws), _lib.ptr(status), st)
+    co = _read_back(coff, status, 'components').tolist()           # the host sync
+    K = co[B]
+    table = torch.empty(max(K, 1), 8, dtype=torch.int32, device=dev)
+    _lib.call('ofx_mesh_cc_stats', _lib.ptr(verts), _lib.ptr(faces), _lib.ptr(label), _lib.ptr(offs[0]),
+              _lib.ptr(offs[1]), B, V, F, K, _lib.ptr(table), _lib.ptr(ws), _lib.ptr(status), st)
+    box = table[:, :6].contiguous().view(torch.float32)
+    cnt = table[:, 6:].to(torch.int64)
+    res, vo, fo = [], 0, 0
+    for b in range(B):
+        cv = cov[vo:vo + nv[b]]
+        fb = faces[fo:fo + nf[b]]
+        rows = slice(co[b], co[b + 1])
+        res.append(dict(comp_of_vert=cv, comp_of_face=cv[fb[:, 0].long()], bbox_min=box[rows, :3],
+                        bbox_max=box[rows, 3:], n_verts=cnt[rows, 0], n_faces=cnt[rows, 1]))
+        vo += nv[b]
+        fo += nf[b]
+    return res
 
 
 def write_obj(path, verts, faces):

@@ -12,7 +12,8 @@ for 3), on device, for a whole batch of independent shapes.
     sdf  : NeuralMPU sweep of the decoded field on the resolution^3 lattice in [-sdf_scale, sdf_scale]^3
            (get_sdfs, octfusion_model_union.py:425-433) -- one kernel launch per shape.
     mesh : (opt-in) marching cubes of every lattice on device (mesh.marching_cubes; export_mesh,
-           octfusion_model_union.py:435-468, runs skimage on the host).
+           octfusion_model_union.py:435-468, runs skimage on the host), with mesh_clean only the largest component
+           of each (clean=True, :459-467).
 """
 import torch
 
@@ -131,7 +132,7 @@ class CascadeSampler:
 
     def _sample_once(self, batch_size, ddim_steps=200, label=None, split_small=None, noises=None, sdf_resolution=None,
                      sdf_scale=0.9, use_graph=None, seed=None, save_index=0, shape_indices=None, timings=None,
-                     mesh=False, mesh_level=0.0, mesh_scale=1.0):
+                     mesh=False, mesh_level=0.0, mesh_scale=1.0, mesh_clean=False):
         """Returns a dict with the per-stage results.  `noises` (optional) = dict of explicit
         init / step noise tensors per stage for reproducible runs.  sdf_resolution (e.g. 256) adds
         out['sdfs'] [B, R, R, R] (needs the VAE).
@@ -144,7 +145,10 @@ class CascadeSampler:
         timings (optional dict): filled with seconds per phase (host-synchronised: adds a few syncs).
         mesh: when the SDF lattice is computed, also out['meshes'] = per-shape (verts, faces) of its level-`mesh_level`
         surface in the lattice's [-sdf_scale, sdf_scale]^3 frame times `mesh_scale` (mesh.mesh_scale: the
-        reference's point_scale); one host sync for the count readback."""
+        reference's point_scale); one host sync for the count readback.
+        mesh_clean: keep only each mesh's largest component (the reference's sample(clean=), export_mesh
+        clean=True, octfusion_model_union.py:459-467) and add out['mesh_components'], the component counts before
+        cleaning; one more host sync (the kept counts)."""
         import time as _time
         noises = dict(noises or {})
         out = {}
@@ -229,8 +233,12 @@ class CascadeSampler:
                 t0 = lap('sdf', t0)
                 if mesh:
                     from . import mesh as _mesh
+                    cc = {}
                     out['meshes'] = _mesh.marching_cubes(out['sdfs'], level=mesh_level, bbmin=-sdf_scale,
-                                                         bbmax=sdf_scale, scale=mesh_scale)
+                                                         bbmax=sdf_scale, scale=mesh_scale, clean=mesh_clean,
+                                                         stats=cc)
+                    if mesh_clean:
+                        out['mesh_components'] = cc['components']
                     t0 = lap('mesh', t0)
         if timings is not None:
             timings.pop('_start', None)
