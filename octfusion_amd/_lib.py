@@ -217,24 +217,45 @@ PROFILE = None
 META = None
 
 
+def _timed(prof, name, args, always):
+    """The one _lib.PROFILE bracket: run entry point `name` between two HIP events on the launching stream, take the
+    label ops._meta left for it and append (name, start, end, meta) -- `always`, or only if it returned 0 (launched)."""
+    global META
+    meta, META = META, None
+    e0 = torch.cuda.Event(enable_timing=True)
+    e1 = torch.cuda.Event(enable_timing=True)
+    e0.record()
+    rc = getattr(lib(), name)(*args)
+    e1.record()
+    if always or rc == 0:
+        prof.append((name, e0, e1, meta))
+    return rc
+
+
 def call(name, *args):
     """Invoke a status-returning entry point; raise OfxError on failure."""
-    global META
     prof = PROFILE
     if prof is not None and _SIGS[name][2]:
-        meta, META = META, None
-        e0 = torch.cuda.Event(enable_timing=True)
-        e1 = torch.cuda.Event(enable_timing=True)
-        e0.record()
-        rc = getattr(lib(), name)(*args)
-        e1.record()
-        prof.append((name, e0, e1, meta))
+        rc = _timed(prof, name, args, True)
     else:
         rc = getattr(lib(), name)(*args)
     if _SIGS[name][2] and rc != 0:
         msg = lib().ofx_status_string(rc).decode()
         raise OfxError('%s failed: %s (%d)' % (name, msg, rc))
     return rc
+
+
+def call_may_decline(name, *args):
+    """Invoke an entry point that returns 0 = launched, 1 = declined (nothing launched: not an error, and no PROFILE
+    record), < 0 = failed.  True if it launched."""
+    prof = PROFILE
+    if prof is not None:
+        rc = _timed(prof, name, args, False)
+    else:
+        rc = getattr(lib(), name)(*args)
+    if rc < 0:
+        raise OfxError('%s failed with status %d' % (name, rc))
+    return rc == 0
 
 
 def ptr(t):

@@ -17,11 +17,21 @@ shared read-only by all 200 denoising steps.  The reference's COO tensors
 reads them.
 """
 import ctypes
+from typing import NamedTuple
 
 import torch
 
 from . import _lib
 from ._lib import call, ptr, stream
+
+
+class OctPlan(NamedTuple):
+    """DualOctree.oct_plan: the aux rows of a GroupNorm launch by sibling octet (ofx_gn_apply_planes_oct)."""
+    plan: torch.Tensor
+    shift: int
+    n_own: int
+    n_left: int
+    offsets: tuple          # (ptr, ent, left_head, left_src) into plan
 
 
 class _Graph(dict):
@@ -305,7 +315,7 @@ class DualOctree:
         if V == 0:
             head_off = (ent_off + 3) & ~3
             plan = torch.zeros(head_off + 4 + 1, dtype=torch.int32, device=dev)
-            self._ext[key] = (plan, shift, 0, 1, (0, ent_off, head_off, head_off + 4))
+            self._ext[key] = OctPlan(plan, shift, 0, 1, (0, ent_off, head_off, head_off + 4))
             return self._ext[key]
         ms = multi_seg[:V].long()
         start, end = seg_ptr[ms].long(), seg_ptr[ms + 1].long()
@@ -344,7 +354,7 @@ class DualOctree:
         pad1 = torch.zeros(head_off - (ent_off + 2 * n_own), dtype=torch.long, device=dev)
         tail = torch.zeros(1, dtype=torch.long, device=dev)              # (left_src is never empty: slot 0 of the zero row)
         plan = torch.cat([ptr_, pad0, ent, pad1, head, l_src, tail]).to(torch.int32)
-        self._ext[key] = (plan, shift, n_own, n_left, (0, ent_off, head_off, head_off + 4 * n_left))
+        self._ext[key] = OctPlan(plan, shift, n_own, n_left, (0, ent_off, head_off, head_off + 4 * n_left))
         return self._ext[key]
 
     def rev(self, d):

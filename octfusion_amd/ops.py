@@ -6,17 +6,36 @@ a CPU implementation -- a CPU tensor raises.
 """
 import contextlib
 import os
+from typing import NamedTuple
 
 import torch
 
 from . import _lib
-from ._lib import call, ptr, stream
+from ._lib import call, call_may_decline, ptr, stream
 
 ACT = {None: 0, 'none': 0, 'silu': 1, 'gelu': 2}
 
-# bench.py sets this to a list to time every fused-GraphConv launch with HIP events on the
-# launching stream: entries are (start_event, end_event, algorithmic_flops, algorithmic_bytes).
+# bench.py sets this to a list to time every fused GraphConv / grid convolution with HIP events on the launching
+# stream: entries are (start_event, end_event, algorithmic_flops, algorithmic_bytes, output width, tag).
 GRAPHCONV_PROFILE = None
+_NO_BRACKET = contextlib.nullcontext()
+
+
+@contextlib.contextmanager
+def _timed_layer(prof, *rec):
+    e0 = torch.cuda.Event(enable_timing=True)
+    e1 = torch.cuda.Event(enable_timing=True)
+    e0.record()
+    yield
+    e1.record()
+    prof.append((e0, e1) + rec)
+
+
+def _layer_bracket(flops, nbytes, width, tag):
+    """Context manager around ALL launches of one operator: an event before the first, one after the last, and the
+    record (e0, e1, flops, nbytes, width, tag) on GRAPHCONV_PROFILE; one shared no-op object while that is None."""
+    prof = GRAPHCONV_PROFILE
+    return _NO_BRACKET if prof is None else _timed_layer(prof, flops, nbytes, width, tag)
 
 
 def _meta(kind, flops=0.0, nbytes=0.0, tag=None):
@@ -36,7 +55,9 @@ def _chk(t, dtype=torch.float32):
 
 
 def _row_major(t):
-    """(tensor, leading dimension) for a 2-D fp32 tensor whose rows are contiguous."""
+    """(tensor, leading dimension) for a 2-D fp32 tensor whose rows are contiguous; (None, 0) for an absent operand."""
+    if t is None:
+        return None, 0
     _chk(t)
     if t.dim() != 2:
         raise ValueError('expected a 2-D tensor')
@@ -49,7 +70,60 @@ def _row_major(t):
     return t, ld
 
 
-_WS = {}
+def _out2d(out, rows, cols, device):
+    """(out, leading dimension) of an operator's fp32 [rows, cols] result: allocated when `out` is None, else the
+    caller's tensor, whose rows must be contiguous (it is written in place, never replaced by a copy)."""
+    if out is None:
+        out = torch.empty(rows, cols, dtype=torch.float32, device=device)
+    t, ld = _row_major(out)
+    if t is not out:
+        raise AssertionError('output must have contiguous rows')
+    return out, ld
+
+
+# ---- scratch: every buffer, stream and pool this module keeps per device or per (device, stream) -----
+_SCRATCH = {}        # (kind, device type, device index[, stream]) -> tensor / stream / pool
+
+
+def _dev_key(device):
+    """(type, index) with a missing index resolved to the current device: 'cuda' and 'cuda:<current>' are one key."""
+    index = device.index
+    if index is None and device.type == 'cuda':
+        index = torch.cuda.current_device()
+    return device.type, index
+
+
+def _stream_id(device):
+    return torch.cuda.current_stream(device).cuda_stream if device.type == 'cuda' else 0
+
+
+def _scratch_key(kind, device, per_stream=False):
+    return (kind,) + _dev_key(device) + ((_stream_id(device),) if per_stream else ())
+
+
+def _scratch(kind, device, per_stream, make):
+    """The `kind` entry of `device` (per_stream: of its current stream), made by make() on first use."""
+    key = _scratch_key(kind, device, per_stream)
+    v = _SCRATCH.get(key)
+    if v is None:
+        v = _SCRATCH[key] = make()
+    return v
+
+
+def _scratch_all(kind, device):
+    """Every per-stream `kind` entry of `device`."""
+    head = _scratch_key(kind, device)
+    return [v for k, v in _SCRATCH.items() if k[:3] == head]
+
+
+def _no_capture(what):
+    """Per-stream scratch must exist BEFORE a capture on that stream (ADVICE r04): allocated inside one, the zero-fill of
+    the flag words becomes a graph node that re-zeroes the sticky error word on every replay, and both buffers land in the
+    graph's private pool.  sampler.sample_loop / bench.py warm up and capture on the SAME stream, so this never fires
+    there; a caller that captures on a stream of its own must run one eager step on it first."""
+    if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+        raise _lib.OfxError('%s of this stream would be allocated inside a hipGraph capture: run one eager step on the '
+                            'capture stream first (sampler.sample_loop does)' % what)
 
 
 PRECISIONS = {'bf16x3': 0, 'fp32': 1, 'fp16': 2, 'fp16x3': 3}
@@ -215,47 +289,32 @@ def graphconv_planes(xp, mode, seg_ptr, col, ext, pw, cin, nt, tf_planes=None, b
     N = xp.shape[0]
     bpc = 4 if planes_pairs(mode) else 2
     ldx = xp.stride(0) * bpc if N > 1 else cin * bpc
-    if out is None:
-        out = torch.empty(N, pw.N, dtype=torch.float32, device=xp.device)
-    out2, ldc = _row_major(out)
-    assert out2 is out
+    out, ldc = _out2d(out, N, pw.N, xp.device)
     nbr_ext, multi_seg, n_multi = ext
     aux = getattr(xp, AUX_ATTR, None)           # written by the producer of xp (group_norm(..., aux_graph=))
     aux_ready = 1 if aux is not None else 0
     if aux is None:
         aux = torch.empty((n_multi + 1) * ldx, dtype=torch.uint8, device=xp.device)
     assert aux.numel() >= (n_multi + 1) * ldx
-    lde = ldr = ldt = 0
-    if emb is not None:
-        emb, lde = _row_major(emb)
+    emb, lde = _row_major(emb)
     if emb is not None or stats is not None:
         _chk(batch_id, torch.int32)
-    if res is not None:
-        res, ldr = _row_major(res)
-    if tf_planes is not None:
-        ldt = tf_planes.stride(0) * bpc
+    res, ldr = _row_major(res)
+    ldt = tf_planes.stride(0) * bpc if tf_planes is not None else 0
     _chk(bias)
     _chk(stats, torch.float64)
-    prof = GRAPHCONV_PROFILE
-    if prof is not None:
-        e0 = torch.cuda.Event(enable_timing=True)
-        e1 = torch.cuda.Event(enable_timing=True)
-        e0.record()
-    ws = workspace(xp.device)
-    sync = sync_words(xp.device)
-    _meta('graphconv', 2.0 * N * pw.K * pw.N, 0, (N, pw.cin, pw.N, 'planes', 'emb' if emb is not None else '',
-                                                  'res' if res is not None else '', 'stats' if stats is not None else ''))
-    call('ofx_graphconv_fwd_planes', ptr(xp), ldx, cin, N, ptr(seg_ptr), ptr(col), ptr(nbr_ext), ptr(multi_seg),
-         n_multi, ptr(aux), aux.numel() * aux.element_size(), ptr(tf_planes), ldt, nt, ptr(pw.t), pw.N, ptr(bias),
-         ptr(emb), lde, ptr(batch_id) if (emb is not None or stats is not None) else None, ptr(res), ldr, ptr(out),
-         ldc, ptr(stats), pw.N, ptr(ws), ws.numel(), ptr(sync), sync.numel() * 4, mode, aux_ready, stream())
-    if prof is not None:
-        e1.record()
-        E = col.numel()
-        s_in = 4.0 if planes_pairs(mode) else 2.0
-        flops = 2.0 * N * pw.K * pw.N
-        nbytes = s_in * (E * pw.cin + pw.K * pw.N) + 4.0 * N * pw.N + 8.0 * E
-        prof.append((e0, e1, flops, nbytes, pw.N, ('graph2' if planes_pairs(mode) else 'graph2h', N, pw.cin, pw.N)))
+    E = col.numel()
+    flops = 2.0 * N * pw.K * pw.N
+    nbytes = bpc * (E * pw.cin + pw.K * pw.N) + 4.0 * N * pw.N + 8.0 * E
+    with _layer_bracket(flops, nbytes, pw.N, ('graph2' if planes_pairs(mode) else 'graph2h', N, pw.cin, pw.N)):
+        ws = workspace(xp.device)
+        sync = sync_words(xp.device)
+        _meta('graphconv', flops, 0, (N, pw.cin, pw.N, 'planes', 'emb' if emb is not None else '',
+                                      'res' if res is not None else '', 'stats' if stats is not None else ''))
+        call('ofx_graphconv_fwd_planes', ptr(xp), ldx, cin, N, ptr(seg_ptr), ptr(col), ptr(nbr_ext), ptr(multi_seg),
+             n_multi, ptr(aux), aux.numel() * aux.element_size(), ptr(tf_planes), ldt, nt, ptr(pw.t), pw.N, ptr(bias),
+             ptr(emb), lde, ptr(batch_id) if (emb is not None or stats is not None) else None, ptr(res), ldr, ptr(out),
+             ldc, ptr(stats), pw.N, ptr(ws), ws.numel(), ptr(sync), sync.numel() * 4, mode, aux_ready, stream())
     return out
 
 
@@ -263,7 +322,6 @@ def graphconv_planes(xp, mode, seg_ptr, col, ext, pw, cin, nt, tf_planes=None, b
 # chain.  Off by default: measured SLOWER on MI355X (hr step 9.44 ms vs 9.19 ms, graph replay) -- the dense GEMM's
 # blocks take CU slots from the co-resident GraphConv blocks instead of only filling its tile-count tail.
 SIDE_STREAM = os.environ.get('OFX_SIDE_STREAM', '0') == '1'
-_SIDE = {}
 
 
 def set_lane_cus(cus):
@@ -274,10 +332,7 @@ def set_lane_cus(cus):
 
 def side_stream(device):
     """The per-device side stream for work that is independent of the main chain (joined before its result is used)."""
-    s = _SIDE.get(device.index)
-    if s is None:
-        s = _SIDE[device.index] = torch.cuda.Stream(device)
-    return s
+    return _scratch('side', device, False, lambda: torch.cuda.Stream(device))
 
 
 # OFX_FORK=1 (default 0: measured slower inside a replayed hipGraph, DESIGN section 8): work that does not depend on the activation chain -- the embedding MLPs of both nets, the 1x1
@@ -286,7 +341,6 @@ def side_stream(device):
 # the step's critical path.  (The sparse net's 1x1 skip convolutions stay on the main stream: next to a persistent
 # GraphConv launch that owns every CU they were measured slower, OFX_SIDE_STREAM above.)
 FORK = int(os.environ.get('OFX_FORK', '0'))      # 0: off; 1: the embedding chains; 2: + the dense net's residual 1x1 convolutions
-_FORK = {}
 
 
 def fork_stream(device, level=1):
@@ -300,9 +354,7 @@ def fork_stream(device, level=1):
     previous result.  Do not allocate on the fork stream outside a fork_stream() ... join pair."""
     if FORK < level or device.type != 'cuda':
         return None, None
-    s = _FORK.get(device.index)
-    if s is None:
-        s = _FORK[device.index] = torch.cuda.Stream(device)
+    s = _scratch('fork', device, False, lambda: torch.cuda.Stream(device))
     main = torch.cuda.current_stream(device)
     if main.cuda_stream == s.cuda_stream:
         return None, None
@@ -310,12 +362,7 @@ def fork_stream(device, level=1):
     return main, s
 
 
-_SYNC = {}
 SYNC_WORDS = 4096
-
-
-def _stream_id(device):
-    return torch.cuda.current_stream(device).cuda_stream if device.type == 'cuda' else 0
 
 
 def sync_words(device):
@@ -323,44 +370,30 @@ def sync_words(device):
     one stream are ordered and may share them, launches on different streams (or graphs captured on different streams)
     run concurrently and must not.  Zero at allocation, every launch leaves them zero; the LAST word is the sticky
     error flag (sync_error())."""
-    key = (device.type, device.index, _stream_id(device))
-    t = _SYNC.get(key)
-    if t is None:
+    def make():
         _no_capture('the flag words')
-        t = _SYNC[key] = torch.zeros(SYNC_WORDS, dtype=torch.int32, device=device)
-    return t
-
-
-def _no_capture(what):
-    """Per-stream scratch must exist BEFORE a capture on that stream (ADVICE r04): allocated inside one, the zero-fill of
-    the flag words becomes a graph node that re-zeroes the sticky error word on every replay, and both buffers land in the
-    graph's private pool.  sampler.sample_loop / bench.py warm up and capture on the SAME stream, so this never fires
-    there; a caller that captures on a stream of its own must run one eager step on it first."""
-    if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-        raise _lib.OfxError('%s of this stream would be allocated inside a hipGraph capture: run one eager step on the '
-                            'capture stream first (sampler.sample_loop does)' % what)
+        return torch.zeros(SYNC_WORDS, dtype=torch.int32, device=device)
+    return _scratch('sync', device, True, make)
 
 
 def sync_error(device):
     """True if a bounded wait of a persistent launch on `device` ever gave up, or a launch left a flag set (host sync)."""
-    return any(int(t.abs().sum().item()) != 0 for k, t in _SYNC.items() if k[:2] == (device.type, device.index))
+    return any(int(t.abs().sum().item()) != 0 for t in _scratch_all('sync', device))
 
 
 def raise_on_sync_error(device):
     """Production check, once per sampling call (sampler.sample_loop, generate, bench): a bounded wait of the persistent
     GraphConv launch gave up -> the results since then are invalid.  Clears the words, switches this process to the
     one-tile-per-block launch (no inter-block waits) and raises."""
-    if not _SYNC or not sync_error(device):
+    if not sync_error(device):
         return
-    for k, t in _SYNC.items():
-        if k[:2] == (device.type, device.index):
-            t.zero_()
+    for t in _scratch_all('sync', device):
+        t.zero_()
     call('ofx_set_gconv_persistent', 0)
     raise _lib.OfxError('a flag wait of the persistent GraphConv launch gave up on %s: the results of this call are '
                         'invalid; the process now uses the one-tile-per-block launch (ofx_set_gconv_persistent(0))' % device)
 
 
-_RANGE = {}
 AUTO_RANGE_FALLBACK = True     # raise_on_range_error switches the process to 'bf16x3' before raising (the retry then fits)
 
 
@@ -371,19 +404,18 @@ class OfxRangeError(_lib.OfxError):
 def range_words(device):
     """The device's sticky fp16x3 range-guard words (include/ofx.h), registered with the library on first use:
     [0] = operands ofx_planes_split found outside the fp16 range (|x| > 65504 or non-finite)."""
-    key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
-    t = _RANGE.get(key)
-    if t is None:
-        with torch.cuda.device(key[1]):
-            t = _RANGE[key] = torch.zeros(4, dtype=torch.int32, device=device)
+    def make():
+        with torch.cuda.device(_dev_key(device)[1]):
+            t = torch.zeros(4, dtype=torch.int32, device=device)
             call('ofx_set_range_words', ptr(t))
-    return t
+        return t
+    return _scratch('range', device, False, make)
 
 
 def reset_range_words(device):
     """Start of a sampling stage: the out-of-range count describes THIS stage only (the word is sticky, and a
     count left by an earlier training forward / test would fail the next sample_loop and switch the process to bf16x3)."""
-    t = _RANGE.get((device.type, device.index if device.index is not None else torch.cuda.current_device()))
+    t = _SCRATCH.get(_scratch_key('range', device))
     if t is not None:
         t.zero_()
 
@@ -392,7 +424,7 @@ def range_error(device, result=None):
     """{'operands_beyond_fp16': n, 'result_non_finite': bool} if operands left the fp16 range on `device` since the words
     were last cleared -- or `result` (a tensor the suspect launches produced) is non-finite: an operand beyond the range
     poisons everything downstream with NaN -- else None (host sync)."""
-    t = _RANGE.get((device.type, device.index if device.index is not None else torch.cuda.current_device()))
+    t = _SCRATCH.get(_scratch_key('range', device))
     n = int(t[0].item()) if t is not None else 0
     bad = result is not None and not bool(torch.isfinite(result).all())
     return {'operands_beyond_fp16': n, 'result_non_finite': bad} if (n or bad) else None
@@ -422,12 +454,12 @@ def raise_on_range_error(device, result=None):
 def workspace(device, nbytes=96 << 20):
     """Split-K / partial-tile scratch, one buffer per (device, stream): launches on one stream are ordered and reuse it,
     launches on different streams (side-stream experiment, graphs captured on their own stream) must not share it."""
-    key = (device.type, device.index, _stream_id(device))
-    t = _WS.get(key)
-    if t is None or t.numel() < nbytes:
+    def make():
         _no_capture('the split-K / hand-off workspace')
-        t = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        _WS[key] = t
+        return torch.empty(nbytes, dtype=torch.uint8, device=device)
+    t = _scratch('ws', device, True, make)
+    if t.numel() < nbytes:
+        t = _SCRATCH[_scratch_key('ws', device, True)] = make()
     return t
 
 
@@ -486,13 +518,8 @@ def gemm(a, pw, bias=None, res=None, out=None, a_rows=None, out_rows=None, m=Non
     M = m if m is not None else (a_rows.numel() if a_rows is not None else a.shape[0])
     if a.shape[1] != pw.K:
         raise ValueError('K mismatch: %d vs %d' % (a.shape[1], pw.K))
-    if out is None:
-        out = torch.empty(M, pw.N, dtype=torch.float32, device=a.device)
-    out2, ldc = _row_major(out)
-    assert out2 is out, 'output must have contiguous rows'
-    ldr = 0
-    if res is not None:
-        res, ldr = _row_major(res)
+    out, ldc = _out2d(out, M, pw.N, a.device)
+    res, ldr = _row_major(res)
     _chk(bias)
     _chk(a_rows, torch.int32)
     _chk(out_rows, torch.int32)
@@ -520,13 +547,8 @@ def gather_gemm(x, tab, ntap, pw, n_out, bias=None, res=None, out=None, out_rows
     cin = x.shape[1]
     assert pw.K == ntap * cin and cin % 32 == 0
     _chk(tab, torch.int32)
-    if out is None:
-        out = torch.empty(n_out, pw.N, dtype=torch.float32, device=x.device)
-    out2, ldc = _row_major(out)
-    assert out2 is out
-    ldr = 0
-    if res is not None:
-        res, ldr = _row_major(res)
+    out, ldc = _out2d(out, n_out, pw.N, x.device)
+    res, ldr = _row_major(res)
     _chk(bias)
     _chk(out_rows, torch.int32)
     ws = workspace(x.device)
@@ -541,7 +563,6 @@ def gather_gemm(x, tab, ntap, pw, n_out, bias=None, res=None, out=None, out_rows
 # [21344, 256] x [256, 2048], 390 vs 402 us at [71088, 256] x [256, 2048] incl. the 10-23 us gather + split of its input rows):
 # off by default, kept for the A/B (OFX_GEMM_PLANES=1)
 GEMM_PLANES = os.environ.get('OFX_GEMM_PLANES', '0') == '1'
-_ROW_TAB = {}
 
 
 class PackedGemmPlanes:
@@ -572,40 +593,23 @@ def gemm_planes(a_planes, pgp, out, out_planes=0, bias=None):
     mode = planes_of(a_planes)
     M, K = a_planes.shape
     assert planes_pairs(mode) and K == pgp.K and a_planes.stride(1) == 1
-    out2, ldc = _row_major(out)
-    assert out2 is out
     dev = a_planes.device
-    key = (dev.index, M)
-    tab = _ROW_TAB.get(key)
+    out, ldc = _out2d(out, M, pgp.N, dev)
+    tabs = _scratch('row_tab', dev, False, dict)         # rows -> identity row table (bounded: cleared beyond 64 shapes)
+    tab = tabs.get(M)
     if tab is None:
-        if len(_ROW_TAB) > 64:
-            _ROW_TAB.clear()
+        if len(tabs) > 64:
+            tabs.clear()
         _no_capture('the row table of a dense planes GEMM')
         tab = torch.zeros(M * 7 + 4, dtype=torch.int32, device=dev)
         tab[:M * 7].view(M, 7)[:, 0] = torch.arange(M, dtype=torch.int32, device=dev)
-        _ROW_TAB[key] = tab
+        tabs[M] = tab
     ws = workspace(dev)
     sync = sync_words(dev)
     _meta('dense_gemm', 2.0 * M * K * pgp.N, 4.0 * (M * K + K * pgp.N + M * pgp.N), (M, K, pgp.N, 'planes'))
-    prof = _lib.PROFILE
-    lib = _lib.lib()
-    args = (ptr(a_planes), a_planes.stride(0) * 4, M, M, K, ptr(tab), ptr(pgp.t), pgp.N, ptr(bias), ptr(out), ldc, out_planes,
-            ptr(ws), ws.numel(), ptr(sync), sync.numel() * 4, mode, stream())
-    if prof is not None:
-        meta, _lib.META = _lib.META, None
-        e0 = torch.cuda.Event(enable_timing=True)
-        e1 = torch.cuda.Event(enable_timing=True)
-        e0.record()
-        rc = lib.ofx_gemm_planes(*args)
-        e1.record()
-        if rc == 0:
-            prof.append(('ofx_gemm_planes', e0, e1, meta))
-    else:
-        _lib.META = None
-        rc = lib.ofx_gemm_planes(*args)
-    if rc < 0:
-        raise _lib.OfxError('ofx_gemm_planes failed with status %d' % rc)
-    return rc == 0
+    return call_may_decline('ofx_gemm_planes', ptr(a_planes), a_planes.stride(0) * 4, M, M, K, ptr(tab), ptr(pgp.t), pgp.N,
+                            ptr(bias), ptr(out), ldc, out_planes, ptr(ws), ws.numel(), ptr(sync), sync.numel() * 4, mode,
+                            stream())
 
 
 LINEAR_SMALL = True          # A/B switch: False sends the few-row linears through the MFMA GEMM again
@@ -619,13 +623,8 @@ def linear_small(a, weight, bias=None, res=None, act_in=None, act_out=None, out=
     M, K = a.shape
     N = w.shape[0]
     assert w.shape[1] == K and M <= 16
-    if out is None:
-        out = torch.empty(M, N, dtype=torch.float32, device=a.device)
-    out2, ldo = _row_major(out)
-    assert out2 is out
-    ldr = 0
-    if res is not None:
-        res, ldr = _row_major(res)
+    out, ldo = _out2d(out, M, N, a.device)
+    res, ldr = _row_major(res)
     _chk(bias)
     _meta('small_linear', 2.0 * M * K * N, 4.0 * (N * K + M * K + M * N), (M, K, N))
     call('ofx_linear_small', ptr(a), lda, M, K, ptr(w), ldw, N, ptr(bias.detach() if bias is not None else None), ptr(res),
@@ -643,74 +642,54 @@ def learned_sinusoid(t, w):
     return out
 
 
-_ZEROS = {}
-
-
 def zero_row(device, n=4096):
-    key = (device.type, device.index)
-    if key not in _ZEROS:
-        _ZEROS[key] = torch.zeros(n, dtype=torch.float32, device=device)
-    return _ZEROS[key]
+    return _scratch('zeros', device, False, lambda: torch.zeros(n, dtype=torch.float32, device=device))
 
 
 def graphconv(x, nbr, seg_ptr, col, pw, cin, type_frac=None, bias=None, emb=None, batch_id=None,
               res=None, out=None, ext=None, stats=None):
-    """ext = (nbr_ext, multi_seg, n_multi) enables the branch-free fast path (cin % 32 == 0).
+    """Fused dual-octree graph convolution (gather -> segment mean -> MFMA contraction).
+    ext = (nbr_ext, multi_seg, n_multi) enables the branch-free fast path (cin % 32 == 0).
     stats (fp64 [B, Cout, 2], zeroed, needs batch_id): the epilogue also accumulates the GroupNorm
     statistics of the output."""
-    """Fused dual-octree graph convolution (gather -> segment mean -> MFMA contraction)."""
     x, ldx = _row_major(x)
     N = x.shape[0]
     if x.shape[1] != cin:
         raise ValueError('cin mismatch')
-    if out is None:
-        out = torch.empty(N, pw.N, dtype=torch.float32, device=x.device)
-    out2, ldc = _row_major(out)
-    assert out2 is out
+    out, ldc = _out2d(out, N, pw.N, x.device)
     ldt = nt_pad = 0
     if type_frac is not None:
         _chk(type_frac)
         ldt = type_frac.stride(0)
         nt_pad = type_frac.shape[1]
-    lde = ldr = 0
-    if emb is not None:
-        emb, lde = _row_major(emb)
+    emb, lde = _row_major(emb)
     if emb is not None or stats is not None:
         _chk(batch_id, torch.int32)
-    if res is not None:
-        res, ldr = _row_major(res)
+    res, ldr = _row_major(res)
     _chk(bias)
     _chk(stats, torch.float64)
-    prof = GRAPHCONV_PROFILE
-    if prof is not None:
-        e0 = torch.cuda.Event(enable_timing=True)
-        e1 = torch.cuda.Event(enable_timing=True)
-        e0.record()
-    ws = workspace(x.device)
-    nbr_ext = multi_seg = aux = None
-    n_multi = 0
-    if ext is not None and cin % 32 == 0:
-        nbr_ext, multi_seg, n_multi = ext
-        aux = torch.empty((n_multi + 1) * ldx, dtype=torch.float32, device=x.device)
-    args = ('ofx_graphconv_fwd', ptr(x), ldx, cin, N, ptr(nbr), ptr(seg_ptr), ptr(col), ptr(nbr_ext), ptr(multi_seg),
-            n_multi, ptr(aux), ptr(type_frac), ldt, nt_pad,
-            ptr(pw.t), pw.Kp, pw.N, ptr(bias), ptr(emb), lde,
-            ptr(batch_id) if (emb is not None or stats is not None) else None,
-            ptr(res), ldr, ptr(out), ldc, ptr(stats), pw.N, ptr(ws), ws.numel(), stream())
-    _meta('graphconv', 2.0 * N * pw.K * pw.N, 0, (N, cin, pw.N, 'reg'))
-    if pw.N <= 64 or cin <= 64:
-        with policy_scope('small_gemm'):
+    E = col.numel()
+    flops = 2.0 * N * pw.K * pw.N                          # pw.K = 7 * (cin + nt)
+    # fused-op algorithmic bytes (SURVEY 8d): one feature row per edge + output + weights + 8 B/edge
+    nbytes = 4.0 * (E * cin + N * pw.N + pw.K * pw.N) + 8.0 * E
+    with _layer_bracket(flops, nbytes, pw.N, ('graph', N, cin, pw.N)):
+        ws = workspace(x.device)
+        nbr_ext = multi_seg = aux = None
+        n_multi = 0
+        if ext is not None and cin % 32 == 0:
+            nbr_ext, multi_seg, n_multi = ext
+            aux = torch.empty((n_multi + 1) * ldx, dtype=torch.float32, device=x.device)
+        args = ('ofx_graphconv_fwd', ptr(x), ldx, cin, N, ptr(nbr), ptr(seg_ptr), ptr(col), ptr(nbr_ext), ptr(multi_seg),
+                n_multi, ptr(aux), ptr(type_frac), ldt, nt_pad,
+                ptr(pw.t), pw.Kp, pw.N, ptr(bias), ptr(emb), lde,
+                ptr(batch_id) if (emb is not None or stats is not None) else None,
+                ptr(res), ldr, ptr(out), ldc, ptr(stats), pw.N, ptr(ws), ws.numel(), stream())
+        _meta('graphconv', flops, 0, (N, cin, pw.N, 'reg'))
+        if pw.N <= 64 or cin <= 64:
+            with policy_scope('small_gemm'):
+                call(*args)
+        else:
             call(*args)
-    else:
-        call(*args)
-    if prof is not None:
-        e1.record()
-        E = col.numel()
-        k_logical = pw.K                                   # 7 * (cin + nt)
-        flops = 2.0 * N * k_logical * pw.N
-        # fused-op algorithmic bytes (SURVEY 8d): one feature row per edge + output + weights + 8 B/edge
-        nbytes = 4.0 * (E * cin + N * pw.N + k_logical * pw.N) + 8.0 * E
-        prof.append((e0, e1, flops, nbytes, pw.N, ('graph', N, cin, pw.N)))
     return out
 
 
@@ -742,39 +721,30 @@ def graphconv_narrow_in(x, seg_ptr, col, weights, cin, nt, node_type=None, bias=
     _chk(w)
     N, cout = x.shape[0], w.shape[1]
     assert x.shape[1] == cin and w.shape[0] == 7 * (cin + nt)
-    if out is None:
-        out = torch.empty(N, cout, dtype=torch.float32, device=x.device)
-    out2, ldc = _row_major(out)
-    assert out2 is out
+    out, ldc = _out2d(out, N, cout, x.device)
     if nt:
         _chk(node_type, torch.uint8)
     _chk(bias)
     _chk(stats, torch.float64)
     if stats is not None:
         _chk(batch_id, torch.int32)
-    prof = GRAPHCONV_PROFILE
-    if prof is not None:
-        e0 = torch.cuda.Event(enable_timing=True)
-        e1 = torch.cuda.Event(enable_timing=True)
-        e0.record()
-    ws = workspace(x.device)
     E = col.numel()
     flops = 2.0 * N * w.shape[0] * cout
     nbytes = 4.0 * (E * cin + N * cout + w.numel()) + 8.0 * E
-    _meta('graphconv_narrow', flops, nbytes, (N, cin, cout, 'narrow_in'))
-    if ext is not None and NARROW_IN_TAB and N >= NARROW_IN_TAB_MIN_ROWS:
-        nbr_ext, multi_seg, n_multi = ext
-        aux = torch.empty((N + n_multi + 1) * (8 if cin <= 4 else 16), dtype=torch.float32, device=x.device)
-        call('ofx_graphconv_narrow_in_tab', ptr(x), ldx, cin, N, ptr(seg_ptr), ptr(col), ptr(nbr_ext), ptr(multi_seg), n_multi,
-             ptr(aux), ptr(node_type) if nt else None, nt, ptr(w), cout, ptr(bias),
-             ptr(batch_id) if stats is not None else None, ptr(out), ldc, ptr(stats), cout, ptr(ws), ws.numel(), stream())
-    else:
-        call('ofx_graphconv_narrow_in', ptr(x), ldx, cin, N, ptr(seg_ptr), ptr(col), ptr(node_type) if nt else None, nt,
-             ptr(w), cout, ptr(bias), ptr(batch_id) if stats is not None else None, ptr(out), ldc, ptr(stats), cout,
-             ptr(ws), ws.numel(), stream())
-    if prof is not None:
-        e1.record()
-        prof.append((e0, e1, flops, nbytes, cout, ('graph', N, cin, cout)))
+    with _layer_bracket(flops, nbytes, cout, ('graph', N, cin, cout)):
+        ws = workspace(x.device)
+        _meta('graphconv_narrow', flops, nbytes, (N, cin, cout, 'narrow_in'))
+        if ext is not None and NARROW_IN_TAB and N >= NARROW_IN_TAB_MIN_ROWS:
+            nbr_ext, multi_seg, n_multi = ext
+            aux = torch.empty((N + n_multi + 1) * (8 if cin <= 4 else 16), dtype=torch.float32, device=x.device)
+            call('ofx_graphconv_narrow_in_tab', ptr(x), ldx, cin, N, ptr(seg_ptr), ptr(col), ptr(nbr_ext), ptr(multi_seg),
+                 n_multi, ptr(aux), ptr(node_type) if nt else None, nt, ptr(w), cout, ptr(bias),
+                 ptr(batch_id) if stats is not None else None, ptr(out), ldc, ptr(stats), cout, ptr(ws), ws.numel(),
+                 stream())
+        else:
+            call('ofx_graphconv_narrow_in', ptr(x), ldx, cin, N, ptr(seg_ptr), ptr(col), ptr(node_type) if nt else None, nt,
+                 ptr(w), cout, ptr(bias), ptr(batch_id) if stats is not None else None, ptr(out), ldc, ptr(stats), cout,
+                 ptr(ws), ws.numel(), stream())
     return out
 
 
@@ -816,33 +786,23 @@ def graphconv_narrow_out(x, seg_ptr, col, pno, C, type_term=None, out=None):
     coalesced), then a gather of cout floats per edge (ofx_graphconv_narrow_out)."""
     N = x.shape[0]
     cout = pno.w.shape[1]
-    prof = GRAPHCONV_PROFILE
-    if prof is not None:
-        e0 = torch.cuda.Event(enable_timing=True)
-        e1 = torch.cuda.Event(enable_timing=True)
-        e0.record()
-    P = gemm(x, pno.pw.get(pno.wd, 'kn'))
-    if out is None:
-        out = torch.empty(N, cout, dtype=torch.float32, device=x.device)
-    out2, ldc = _row_major(out)
-    assert out2 is out
-    _chk(type_term)
-    assert type_term is None or (type_term.is_contiguous() and tuple(type_term.shape) == (N, cout))
     E = col.numel()
     flops = 2.0 * N * pno.w.shape[0] * cout
     # bytes of the algorithm that RUNS (project-then-aggregate), each array once: the aggregation reads P, the CSR
     # (7 N segment bounds + E columns) and the cached node-type / bias term and writes the output; the whole operator
-    # (`prof` bracket: projection GEMM + aggregation) also reads x and writes P.  (Until round 5 this line carried the
+    # (the layer bracket: projection GEMM + aggregation) also reads x and writes P.  (Until round 5 this line carried the
     # reference operator's 4 E C bytes, which this path never moves: its "fraction of the HBM roof" read 2.0.)
-    pwid = P.shape[1]
+    pwid = pno.width                                       # columns of P
     agg_bytes = 4.0 * (N * pwid + E + 7 * N + 2 * N * cout)
     nbytes = agg_bytes + 4.0 * (N * C + N * pwid + pno.w.numel())
-    _meta('graphconv_narrow', flops, agg_bytes, (N, C, cout, 'narrow_out'))
-    call('ofx_graphconv_narrow_out', ptr(P), P.stride(0), cout, N, ptr(seg_ptr), ptr(col), ptr(type_term), ptr(out), ldc,
-         stream())
-    if prof is not None:
-        e1.record()
-        prof.append((e0, e1, flops, nbytes, cout, ('graph', N, C, cout)))
+    with _layer_bracket(flops, nbytes, cout, ('graph', N, C, cout)):
+        P = gemm(x, pno.pw.get(pno.wd, 'kn'))
+        out, ldc = _out2d(out, N, cout, x.device)
+        _chk(type_term)
+        assert type_term is None or (type_term.is_contiguous() and tuple(type_term.shape) == (N, cout))
+        _meta('graphconv_narrow', flops, agg_bytes, (N, C, cout, 'narrow_out'))
+        call('ofx_graphconv_narrow_out', ptr(P), P.stride(0), cout, N, ptr(seg_ptr), ptr(col), ptr(type_term), ptr(out),
+             ldc, stream())
     return out
 
 
@@ -990,36 +950,25 @@ def gridconv(x, tables, n_out, pw, bias=None, emb=None, batch_id=None, res=None,
     x, ldx = _row_major(x)
     if x.shape[1] != pw.cin:
         raise ValueError('cin mismatch')
-    if out is None:
-        out = torch.empty(n_out, pw.N, dtype=torch.float32, device=x.device)
-    out2, ldc = _row_major(out)
-    assert out2 is out
-    lde = ldr = 0
+    out, ldc = _out2d(out, n_out, pw.N, x.device)
+    emb, lde = _row_major(emb)
     if emb is not None:
-        emb, lde = _row_major(emb)
         _chk(batch_id, torch.int32)
-    if res is not None:
-        res, ldr = _row_major(res)
+    res, ldr = _row_major(res)
     _chk(bias)
     ws = workspace(x.device)
     fast = pw.cin % 32 == 0 and ldx % 4 == 0
-    prof = GRAPHCONV_PROFILE
-    if prof is not None:
-        e0 = torch.cuda.Event(enable_timing=True)
-        e1 = torch.cuda.Event(enable_timing=True)
-        e0.record()
-    _meta('gridconv_27tap', 2.0 * n_out * 27 * pw.cin * pw.N,
-          4.0 * (x.shape[0] * pw.cin + n_out * pw.N * (2 if res is not None else 1) + 27.0 * pw.cin * pw.N) + 4.0 * 27 * n_out,
-          (n_out, pw.cin, pw.N))
-    call('ofx_gridconv_fwd', ptr(x), ldx, pw.cin, x.shape[0], n_out, None if fast else ptr(tables(False)),
-         ptr(tables(True)) if fast else None, ptr(zero_row(x.device)), ptr(pw.t), pw.N, ptr(bias), ptr(emb), lde,
-         ptr(batch_id) if emb is not None else None, ptr(res), ldr, ptr(out), ldc, ptr(ws), ws.numel(), stream())
-    if prof is not None:
-        e1.record()
-        # same kernel as the GraphConv (27 taps): algorithmic = one source row per tap + output + weights + indices
-        flops = 2.0 * n_out * 27 * pw.cin * pw.N
-        nbytes = 4.0 * (27.0 * n_out * pw.cin + n_out * pw.N + 27.0 * pw.cin * pw.N) + 4.0 * 27 * n_out
-        prof.append((e0, e1, flops, nbytes, pw.N, ('grid', n_out, pw.cin, pw.N)))
+    flops = 2.0 * n_out * 27 * pw.cin * pw.N
+    # the layer record counts it as the GraphConv kernel it is (27 taps): one source row per tap + output + weights +
+    # indices; the per-launch label counts the input tensor once (+ the residual when there is one)
+    nbytes = 4.0 * (27.0 * n_out * pw.cin + n_out * pw.N + 27.0 * pw.cin * pw.N) + 4.0 * 27 * n_out
+    with _layer_bracket(flops, nbytes, pw.N, ('grid', n_out, pw.cin, pw.N)):
+        _meta('gridconv_27tap', flops,
+              4.0 * (x.shape[0] * pw.cin + n_out * pw.N * (2 if res is not None else 1) + 27.0 * pw.cin * pw.N) + 4.0 * 27 * n_out,
+              (n_out, pw.cin, pw.N))
+        call('ofx_gridconv_fwd', ptr(x), ldx, pw.cin, x.shape[0], n_out, None if fast else ptr(tables(False)),
+             ptr(tables(True)) if fast else None, ptr(zero_row(x.device)), ptr(pw.t), pw.N, ptr(bias), ptr(emb), lde,
+             ptr(batch_id) if emb is not None else None, ptr(res), ldr, ptr(out), ldc, ptr(ws), ws.numel(), stream())
     return out
 
 
@@ -1034,10 +983,7 @@ def attention(qkv, batch_size, T, heads, out=None):
     qkv, ldq = _row_major(qkv)
     C = qkv.shape[1] // 3
     ch = C // heads
-    if out is None:
-        out = torch.empty(qkv.shape[0], C, dtype=torch.float32, device=qkv.device)
-    out2, ldo = _row_major(out)
-    assert out2 is out
+    out, ldo = _out2d(out, qkv.shape[0], C, qkv.device)
     _meta('attention', 4.0 * batch_size * heads * T * T * ch, 4.0 * qkv.shape[0] * 4 * C, (batch_size, T, heads, ch))
     call('ofx_attention', ptr(qkv), ldq, batch_size, T, heads, ch, ptr(out), ldo, stream())
     return out
@@ -1087,6 +1033,43 @@ GN_OCT_FINALIZE_MAX_ELEMS = int(os.environ.get('OFX_GN_OCT_FINALIZE_MAX_ELEMS', 
 AUX_PLAN = {'1': 'oct', '0': ''}.get(os.environ.get('OFX_AUX_PLAN', 'oct'), os.environ.get('OFX_AUX_PLAN', 'oct'))
 
 
+class AuxGraph(NamedTuple):
+    """group_norm(aux_graph=): the graph of the planes GraphConv that consumes the result -- the launch then also writes
+    that convolution's aux rows (zero row + multi-neighbour means) -- and, optionally, who writes them: the sibling
+    octets (dual_octree.DualOctree.oct_plan) or the 64-row blocks (DualOctree.aux_plan)."""
+    seg_ptr: torch.Tensor
+    col: torch.Tensor
+    multi_seg: torch.Tensor
+    n_multi: int
+    oct_plan: tuple = None
+    block_plan: tuple = None
+
+
+def _gn_launch(planes, aux_graph, elems):
+    """(launch, finalize) of the apply step of a GroupNorm over `elems` elements.  launch: 'fp32' (ofx_gn_apply), or for a
+    planes result 'oct' (ofx_gn_apply_planes_oct), 'block' (ofx_gn_apply_planes with the block plan) or 'plain'
+    (ofx_gn_apply_planes without a plan); finalize: an ofx_gn_finalize launch precedes it -- otherwise mean / rstd are
+    derived from the sums inside the launch (ofx.h).
+
+    A launch that also writes aux rows keeps the 4 us finalize launch: an aux block's work is a chain of dependent loads
+    (segment -> edge range -> column -> row) and deriving the statistics first makes the chain longer.  Measured twice:
+    round 3, every aux thread deriving its own statistics: 75 us vs 61 us at depth 6, C = 128; round 4, once per aux
+    block from its first / last segment's batch elements (the kernel still does that when no mean / rstd is passed):
+    gn_apply 1.15 -> 1.47 ms per hr step, against 0.115 ms for the 18 finalize launches it removes.  The exception is
+    the octet launch on tensors up to GN_OCT_FINALIZE_MAX_ELEMS, which derives them once per block (GN_OCT_FINALIZE).
+    GN_FINALIZE_LAUNCH = True forces the finalize launch everywhere, GN_FUSE_AUX_FINALIZE = True removes it (A/B); the
+    octet launch has no fused variant above that bar, so an octet plan then takes the plain launch."""
+    g = aux_graph if planes else None
+    oct_plan, block_plan = (g.oct_plan, g.block_plan) if g is not None and AUX_PLAN else (None, None)
+    oct_fin = GN_OCT_FINALIZE and AUX_PLAN == 'oct' and oct_plan is not None and elems <= GN_OCT_FINALIZE_MAX_ELEMS
+    finalize = GN_FINALIZE_LAUNCH or (g is not None and not GN_FUSE_AUX_FINALIZE and not oct_fin)
+    if not planes:
+        return 'fp32', finalize
+    if oct_plan is not None:
+        return ('oct' if finalize or oct_fin else 'plain'), finalize
+    return ('block' if block_plan is not None else 'plain'), finalize
+
+
 def group_norm(x, batch_id, count, batch_size, weight, bias, groups, eps=1e-5, act=None, out=None,
                count_eps=None, stats=None, rows_per_batch=None, planes=0, aux_graph=None):
     """DualOctreeGroupNorm (+ optional fused activation).  count_eps=0 gives torch.nn.GroupNorm.
@@ -1101,10 +1084,7 @@ def group_norm(x, batch_id, count, batch_size, weight, bias, groups, eps=1e-5, a
     if (rows_per_batch is not None and stats is None and not planes and rows_per_batch * (C // groups) <= (1 << 16)
             and rows_per_batch < GN_ROWS_TWO_KERNELS):
         assert n == rows_per_batch * batch_size
-        if out is None:
-            out = torch.empty(n, C, dtype=torch.float32, device=dev)
-        out2, ldo = _row_major(out)
-        assert out2 is out
+        out, ldo = _out2d(out, n, C, dev)
         _meta('gn_fused_rows', 0, 8.0 * n * C, (n, C))
         call('ofx_gn_fused_rows', ptr(x), ldx, rows_per_batch, batch_size, C, groups, eps, count_eps,
              ptr(weight.detach().reshape(-1)), ptr(bias.detach().reshape(-1)), ACT[act], ptr(out), ldo, stream())
@@ -1121,63 +1101,43 @@ def group_norm(x, batch_id, count, batch_size, weight, bias, groups, eps=1e-5, a
         else:
             sums = torch.empty(batch_size * C * 2, dtype=torch.float64, device=dev)
             call('ofx_gn_stats', ptr(x), ldx, n, C, ptr(batch_id), batch_size, ptr(sums), stream())
-    # mean / rstd are derived from the sums inside the apply launch (ofx.h: no ofx_gn_finalize launch) -- except when
-    # the launch also writes the consuming GraphConv's aux rows: an aux block's work is a chain of dependent loads
-    # (segment -> edge range -> column -> row) and deriving the statistics first makes the chain longer.  Measured twice:
-    # round 3, every aux thread deriving its own statistics: 75 us vs 61 us at depth 6, C = 128; round 4, once per aux
-    # block from its first / last segment's batch elements (the kernel still does that when no mean / rstd is passed):
-    # gn_apply 1.15 -> 1.47 ms per hr step, against 0.115 ms for the 18 finalize launches it removes.  So that case keeps
-    # the 4 us finalize launch.  GN_FINALIZE_LAUNCH = True forces it everywhere, GN_FUSE_AUX_FINALIZE = True removes it (A/B).
+    w = weight.detach().reshape(-1)
+    b = bias.detach().reshape(-1)
     mean = rstd = None
-    oct_fin = (GN_OCT_FINALIZE and planes and aux_graph is not None and AUX_PLAN == 'oct' and len(aux_graph) > 4
-               and aux_graph[4] is not None and len(aux_graph[4]) == 5 and n * C <= GN_OCT_FINALIZE_MAX_ELEMS)
-    if GN_FINALIZE_LAUNCH or (planes and aux_graph is not None and not GN_FUSE_AUX_FINALIZE and not oct_fin):
+    launch, finalize = _gn_launch(planes, aux_graph, n * C)
+    if finalize:
         mean = torch.empty(batch_size * C, dtype=torch.float32, device=dev)
         rstd = torch.empty(batch_size * C, dtype=torch.float32, device=dev)
         _meta('gn_finalize', 0, 24.0 * batch_size * C, (batch_size, C))
         call('ofx_gn_finalize', ptr(sums), ptr(count), batch_size, C, groups, eps, count_eps, ptr(mean), ptr(rstd),
              stream())
-    w = weight.detach().reshape(-1)
-    b = bias.detach().reshape(-1)
     if planes:
-        # the consumer is the planes GraphConv: write its operand format directly.  aux_graph = (seg_ptr, col,
-        # multi_seg, n_multi) of the consumer's graph: the same launch then also writes its aux rows (zero row +
-        # multi-neighbour means), which needs a destination other than x.
+        # the consumer is the planes GraphConv: write its operand format directly.  With aux_graph (an AuxGraph: the
+        # consumer's graph) the same launch also writes its aux rows, which needs a destination other than x.
         if aux_graph is not None and out is not None and out.data_ptr() == x.data_ptr():
             out = None
         out, ldo = _planes_out(n, C, planes, dev, out if planes_pairs(planes) else None)
-        aux = seg_ptr = col = multi_seg = plan = None
-        n_multi = n_left = 0
+        aux = seg_ptr = col = multi_seg = None
+        n_multi = 0
         if aux_graph is not None:
             seg_ptr, col, multi_seg, n_multi = aux_graph[:4]
-            oct_plan = None
-            if len(aux_graph) > 4 and aux_graph[4] is not None and AUX_PLAN:
-                if len(aux_graph[4]) == 5:
-                    oct_plan = aux_graph[4]          # dual_octree.DualOctree.oct_plan
-                else:
-                    plan, n_left = aux_graph[4]      # (int32 plan, leftover count): dual_octree.DualOctree.aux_plan
             aux = torch.empty((n_multi + 1) * ldo, dtype=torch.uint8, device=dev)
+            setattr(out, AUX_ATTR, aux)
+        setattr(out, PLANES_ATTR, planes)
         _meta('gn_apply', 0, 8.0 * n * C + (n_multi + 1) * float(ldo), (n, C, 'planes+aux' if aux is not None else 'planes'))
-        if aux is not None and oct_plan is not None and (mean is not None or oct_fin):
-            op, shift, n_own, n_left, (o_ptr, o_ent, o_head, o_src) = oct_plan
+        if launch == 'oct':
+            op, shift, n_own, n_left, (o_ptr, o_ent, o_head, o_src) = aux_graph.oct_plan
             base = op.data_ptr()
             call('ofx_gn_apply_planes_oct', ptr(x), ldx, n, C, ptr(batch_id), ptr(mean), ptr(rstd), ptr(sums), ptr(count),
                  groups, eps, count_eps, ptr(w), ptr(b), ACT[act], planes, ptr(out), ldo, n_multi, ptr(aux), base + 4 * o_ptr,
                  base + 4 * o_ent, n_own, shift, base + 4 * o_head, base + 4 * o_src, n_left, stream())
-            setattr(out, PLANES_ATTR, planes)
-            setattr(out, AUX_ATTR, aux)
-            return out
-        call('ofx_gn_apply_planes', ptr(x), ldx, n, C, ptr(batch_id), ptr(mean), ptr(rstd), ptr(sums), ptr(count), groups, eps,
-             count_eps, ptr(w), ptr(b), ACT[act], planes, ptr(out), ldo, ptr(seg_ptr), ptr(col), ptr(multi_seg), n_multi,
-             ptr(aux), ptr(plan), n_left, stream())
-        setattr(out, PLANES_ATTR, planes)
-        if aux is not None:
-            setattr(out, AUX_ATTR, aux)
+        else:
+            plan, n_left = aux_graph.block_plan if launch == 'block' else (None, 0)
+            call('ofx_gn_apply_planes', ptr(x), ldx, n, C, ptr(batch_id), ptr(mean), ptr(rstd), ptr(sums), ptr(count), groups,
+                 eps, count_eps, ptr(w), ptr(b), ACT[act], planes, ptr(out), ldo, ptr(seg_ptr), ptr(col), ptr(multi_seg),
+                 n_multi, ptr(aux), ptr(plan), n_left, stream())
         return out
-    if out is None:
-        out = torch.empty(n, C, dtype=torch.float32, device=dev)
-    out2, ldo = _row_major(out)
-    assert out2 is out
+    out, ldo = _out2d(out, n, C, dev)
     _meta('gn_apply', 0, 8.0 * n * C, (n, C, 'fp32'))
     call('ofx_gn_apply', ptr(x), ldx, n, C, ptr(batch_id), ptr(mean), ptr(rstd), ptr(sums), ptr(count), groups, eps, count_eps,
          ptr(w), ptr(b), ACT[act], ptr(out), ldo, stream())
@@ -1228,15 +1188,8 @@ class _StatsPool:
         self.gen = 0
 
 
-_stats_pools = {}
-
-
 def _stats_pool_of(device):
-    key = (device.type, device.index, _stream_id(device))
-    p = _stats_pools.get(key)
-    if p is None:
-        p = _stats_pools[key] = _StatsPool()
-    return p
+    return _scratch('stats', device, True, _StatsPool)
 
 
 @contextlib.contextmanager
@@ -1298,9 +1251,8 @@ def cat_channels(a, b, buf=None):
 def rows_copy(src, dst, n, smap=None, dmap=None, C=None, planes=0):
     """dst[dmap(i)] = src[smap(i)]; planes (2 / 3): the destination rows are written as hi / lo pair planes."""
     src, lds = _row_major(src)
-    dst2, ldd = _row_major(dst)
-    assert dst2 is dst
     C = C if C is not None else src.shape[1]
+    dst, ldd = _out2d(dst, n, C, src.device)
     _meta('rows_copy', 0, 8.0 * n * C, (n, C))
     if planes:
         call('ofx_rows_copy_planes', ptr(src), lds, ptr(smap), ptr(dst), ldd, ptr(dmap), n, C, planes, stream())
@@ -1340,10 +1292,7 @@ def voxel2octree_cf(vox, depth, out=None):
     _chk(vox)
     vox = vox.contiguous()
     B, C = vox.shape[:2]
-    if out is None:
-        out = torch.empty(B * (8 ** depth), C, dtype=torch.float32, device=vox.device)
-    out2, ld = _row_major(out)
-    assert out2 is out
+    out, ld = _out2d(out, B * (8 ** depth), C, vox.device)
     call('ofx_voxel2octree_cf', ptr(vox), C, B, depth, ptr(out), ld, stream())
     return out
 

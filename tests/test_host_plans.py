@@ -255,3 +255,12 @@ def test_lane_count_rules(monkeypatch):
     assert sampler.lane_count(8, object(), True) == 1                 # a doctree that cannot split itself
     monkeypatch.setattr(sampler, 'LANES', 4)
     assert sampler.lane_count(3, doc, True) == 3
+
+
+def test_scratch_key_is_the_same_for_cuda_and_cuda_current(monkeypatch):
+    """ops._dev_key: a device without an index means the current one, so scratch registered through torch.device('cuda')
+    is found by a check made with 'cuda:<current>' (sync_error / raise_on_sync_error) -- needs no device."""
+    from octfusion_amd import ops
+    monkeypatch.setattr(torch.cuda, 'current_device', lambda: 2)
+    assert ops._dev_key(torch.device('cuda')) == ops._dev_key(torch.device('cuda:2')) == ('cuda', 2)
+    assert ops._dev_key(torch.device('cuda:0')) == ('cuda', 0) != ops._dev_key(torch.device('cuda'))

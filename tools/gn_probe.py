@@ -27,11 +27,11 @@ for d, C in [(6, 128), (6, 256), (6, 384), (5, 256), (5, 512), (4, 512)]:
     f = lambda **kw: ops.group_norm(x, bid, cnt, 8, gn.weights, gn.bias, gn.group, act='silu', stats=stats, **kw)
     t0 = timeit(lambda: f())
     t2 = timeit(lambda: f(planes=2))
-    t2a = timeit(lambda: f(planes=2, aux_graph=(seg_ptr, col, multi_seg, V)))
+    t2a = timeit(lambda: f(planes=2, aux_graph=ops.AuxGraph(seg_ptr, col, multi_seg, V)))
     plan = doc.aux_plan(d)
-    t2p = timeit(lambda: f(planes=2, aux_graph=(seg_ptr, col, multi_seg, V, plan)))
-    ya = f(planes=2, aux_graph=(seg_ptr, col, multi_seg, V))
-    yb = f(planes=2, aux_graph=(seg_ptr, col, multi_seg, V, plan))
+    t2p = timeit(lambda: f(planes=2, aux_graph=ops.AuxGraph(seg_ptr, col, multi_seg, V, block_plan=plan)))
+    ya = f(planes=2, aux_graph=ops.AuxGraph(seg_ptr, col, multi_seg, V))
+    yb = f(planes=2, aux_graph=ops.AuxGraph(seg_ptr, col, multi_seg, V, block_plan=plan))
     def aux_vals(y):
         a_ = getattr(y, ops.AUX_ATTR).view(torch.float32).view(V + 1, -1)[:, :C]
         setattr(a_, ops.PLANES_ATTR, 2)
@@ -41,11 +41,11 @@ for d, C in [(6, 128), (6, 256), (6, 384), (5, 256), (5, 512), (4, 512)]:
           'aux rows max |diff| %.2e' % (t2p, t2a, plan[1], V + 1, torch.equal(ya, yb), diff))
     # A/B: the separate ofx_gn_finalize launch (round 2) vs mean / rstd derived inside the apply launch (round 3)
     ops.GN_FINALIZE_LAUNCH = True
-    t2a_sep = timeit(lambda: f(planes=2, aux_graph=(seg_ptr, col, multi_seg, V)))
+    t2a_sep = timeit(lambda: f(planes=2, aux_graph=ops.AuxGraph(seg_ptr, col, multi_seg, V)))
     t0_sep = timeit(lambda: f())
     ops.GN_FINALIZE_LAUNCH = False
     print('   finalize: fused %.1f / %.1f us (fp32 / planes+aux), separate launch %.1f / %.1f us' % (t0, t2a, t0_sep, t2a_sep))
-    y = f(planes=2, aux_graph=(seg_ptr, col, multi_seg, V))
+    y = f(planes=2, aux_graph=ops.AuxGraph(seg_ptr, col, multi_seg, V))
     aux_fold = getattr(y, ops.AUX_ATTR).clone()
     # stand-alone pre-pass on the planes for comparison (timed through a conv-less call of the kernel is not exposed;
     # the aux rows of both paths must agree)

@@ -1,5 +1,5 @@
 import os, sys
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from octfusion_amd import _lib, ops, synthetic, modules as M
 from octfusion_amd.dual_octree import DualOctree
@@ -25,5 +25,5 @@ for d, C in [(8, 64), (8, 128), (8, 192), (7, 128), (7, 256)]:
     _lib.call('ofx_gn_stats', x.data_ptr(), C, N, C, bid.data_ptr(), 8, stats.data_ptr(), torch.cuda.current_stream().cuda_stream)
     f = lambda **kw: ops.group_norm(x, bid, cnt, 8, gn.weights, gn.bias, gn.group, act='silu', stats=stats, **kw)
     plan = doc.aux_plan(d)
-    t0 = timeit(lambda: f()); t3 = timeit(lambda: f(planes=3)); t3p = timeit(lambda: f(planes=3, aux_graph=(seg_ptr, col, multi_seg, V, plan)))
+    t0 = timeit(lambda: f()); t3 = timeit(lambda: f(planes=3)); t3p = timeit(lambda: f(planes=3, aux_graph=ops.AuxGraph(seg_ptr, col, multi_seg, V, block_plan=plan)))
     print('d%d C=%d N=%d V=%d: fp32 %.0f us (%.2f TB/s)  planes %.0f us  planes+aux(plan) %.0f us  (+%.0f%% for %.0f%% more rows)' % (d, C, N, V, t0, 8e-6*N*C/t0, t3, t3p, 100*(t3p/t3-1), 100.0*V/N))

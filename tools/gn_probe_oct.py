@@ -31,12 +31,12 @@ def run(doc, shapes, tag):
         f = lambda **kw: ops.group_norm(x, bid, cnt, 8, gn.weights, gn.bias, gn.group, act='silu', stats=stats, **kw)
         op, bp = doc.oct_plan(d), doc.aux_plan(d)
         t_plain = timeit(lambda: f(planes=3))
-        t_oct = timeit(lambda: f(planes=3, aux_graph=(seg_ptr, col, multi_seg, V, op)))
-        t_blk = timeit(lambda: f(planes=3, aux_graph=(seg_ptr, col, multi_seg, V, bp)))
-        t_sep = timeit(lambda: f(planes=3, aux_graph=(seg_ptr, col, multi_seg, V)))
-        t_oct2 = timeit(lambda: f(planes=3, aux_graph=(seg_ptr, col, multi_seg, V, op)))
+        t_oct = timeit(lambda: f(planes=3, aux_graph=ops.AuxGraph(seg_ptr, col, multi_seg, V, oct_plan=op)))
+        t_blk = timeit(lambda: f(planes=3, aux_graph=ops.AuxGraph(seg_ptr, col, multi_seg, V, block_plan=bp)))
+        t_sep = timeit(lambda: f(planes=3, aux_graph=ops.AuxGraph(seg_ptr, col, multi_seg, V)))
+        t_oct2 = timeit(lambda: f(planes=3, aux_graph=ops.AuxGraph(seg_ptr, col, multi_seg, V, oct_plan=op)))
         ops.GN_OCT_FINALIZE = False
-        t_oct_sep = timeit(lambda: f(planes=3, aux_graph=(seg_ptr, col, multi_seg, V, op)))
+        t_oct_sep = timeit(lambda: f(planes=3, aux_graph=ops.AuxGraph(seg_ptr, col, multi_seg, V, oct_plan=op)))
         ops.GN_OCT_FINALIZE = True
         r = dict(tree=tag, depth=d, C=C, N=N, V=V, oct_owned=op[2], oct_left=op[3], block_left=bp[1], us_no_aux=t_plain,
                  us_oct=min(t_oct, t_oct2), us_oct_separate_finalize=t_oct_sep, us_block=t_blk, us_sep=t_sep,
