@@ -212,7 +212,9 @@ int ofx_graph_primary_ext_w(const int32_t* seg_ptr, const int32_t* col, const fl
  * _bwd_data: dx [n, cin] = fused gather-GEMM of dy over the REVERSE graph (weighted segment sums) with the
  *   transposed weights WpT = ofx_pack_weights of W^T stacked over directions (K = 7*cout, N = cin, cin_pack =
  *   cout, nt = 0).  nbr_rev / nbr_ext_rev / multi_seg come from the _w table builders above; aux: scratch of
- *   (n_multi + 1) * ldy floats.
+ *   (n_multi + 1) * ldy floats.  Without nbr_ext_rev, or with cout % 32 != 0 (or dy / ldy / aux not 16-B aligned),
+ *   it takes the col path of ofx_graphconv_fwd: ws 16-B aligned with ws_bytes >= 588 * KpT, else OFX_EINVAL with
+ *   nothing launched.
  * _bwd_weight: dWp [Kp, cout] = col_data^T @ dy in the PACKED k order of ofx_pack_weights (k = dir*cin + c,
  *   zero rows up to pad32(7*cin), then the 7*nt node-type rows), bf16 hi + lo pair MFMA (three products, ~16
  *   significand bits; exact fp32 MFMA under ofx_set_precision(1)), deterministic slice-ordered reduction.  ws holds
@@ -254,7 +256,8 @@ int ofx_seg_primary_ext_w(const int32_t* seg_ptr, const int32_t* col, const floa
                           const int32_t* rank, int32_t* nbr_ext, int32_t* multi_seg, void* stream);
 /* Backward of the 27-tap grid convolution (torch autograd of nn.Conv3d(k=3, padding=1[, stride 2]) and of
  * nearest-upsample + conv: graph_unet_lr.py / modules.py:63-95).  WpT = ofx_pack_conv3d of weight.transpose(0,1);
- * dWp [pad32(27*cin), cout], row k = tap*cin + c. */
+ * dWp [pad32(27*cin), cout], row k = tap*cin + c.  _bwd_data's workspace rule is ofx_graphconv_bwd_data's
+ * (col path: ws_bytes >= 588 * pad32(27*cout)). */
 int ofx_gridconv_bwd_data(const float* dy, int64_t ldy, int cout, int64_t n_out, int64_t n_in, const int32_t* nbr_rev,
                           const int32_t* rev_ptr, const int32_t* rev_row, const float* rev_w,
                           const int32_t* nbr_ext_rev, const int32_t* multi_seg, int64_t n_multi, float* aux,
@@ -372,10 +375,15 @@ int ofx_gemm_f32_planes(const float* A, int64_t lda, const int32_t* a_rows, int6
  * written to HBM); the contraction runs on fp32 MFMA.  emb/batch_id fuse the
  * reference's per-batch-element time-embedding add (modules.py:754-758), res
  * the residual / skip add (:763).  type_frac may be NULL (nt <= 1).
- * nbr = ofx_graph_primary table (generic path: any cin).  nbr_ext / multi_seg / aux
+ * nbr = ofx_graph_primary table (col path: any cin).  nbr_ext / multi_seg / aux
  * (scratch of (n_multi+1)*cin floats) enable the branch-free fast path when
  * cin % 32 == 0: a pre-pass averages the few multi-neighbour segments into aux, the
  * main kernel then gathers exactly one row per (row,dir).  ws: split-K workspace.
+ * Col path (no nbr_ext, cin % 32 != 0, or x / ldx / aux not 16-B aligned): col_data rows
+ * are materialised chunk by chunk in ws and contracted by the dense kernel, so ws is
+ * REQUIRED there: 16-B aligned and ws_bytes >= 588 * Kp (128 col rows of Kp floats after
+ * the 1/8 set aside for split-K / statistics partials), else OFX_EINVAL with nothing
+ * launched; a larger ws only means fewer, larger chunks.
  * stats (optional, needs batch_id): the epilogue also accumulates the GroupNorm statistics
  * of the OUTPUT, stats[(b*stats_ld + n)*2 + {0,1}] += (v, v^2) in fp64 (caller zeroes it),
  * in the layout ofx_gn_finalize reads -- the consuming norm then skips ofx_gn_stats. */
@@ -546,13 +554,16 @@ int ofx_set_gconv2_tile(int wm);
  * (graph_unet_lr.py:176-181) are identities and a 3x3x3 Conv3d is the same fused
  * gather-GEMM with 27 taps.
  * ofx_grid_conv_table: nbr27[row*27 + tap] (tap = (kx*3+ky)*3+kz); out-of-grid taps get
- *   `pad`: -1 for the generic kernel, n_in (the zero row) for the branch-free kernel.
+ *   `pad`: -1 for the col path, n_in (the zero row) for the branch-free kernel.
  *   mode 0: nn.Conv3d(k3,p1) at depth_out; mode 1: ConvDownsample (k3,s2,p1,
  *   modules.py:81-95) depth_out+1 -> depth_out; mode 2: ConvUpsample (nearest x2 then
  *   k3,p1, modules.py:63-78) depth_out-1 -> depth_out.
  * ofx_pack_conv3d: nn.Conv3d weight [cout,cin,3,3,3] -> packed k = tap*cin + c.
  * ofx_gridconv_fwd: out[r,:] = sum_tap x[nbr27[r,tap],:] @ W_tap + bias + emb[bid[r]] + res[r]
  *   (emb fuses ResnetBlock's time_mlp add, modules.py:507-511; res the skip, :513).
+ *   cin % 32 == 0 with nbr27_ext and zero_row: the branch-free kernel.  Otherwise the col path of
+ *   ofx_graphconv_fwd over nbr27: ws 16-B aligned with ws_bytes >= 588 * ofx_conv3d_packed_k(cin), else
+ *   OFX_EINVAL with nothing launched.
  * ofx_attention: QKVAttention (modules.py:538-547) on rows; see csrc/ofx_dense.hip. */
 int ofx_grid_conv_table(int mode, int depth_out, int batch_size, int32_t pad, int32_t* nbr27,
                         void* stream);

@@ -1,21 +1,25 @@
 // libofx: register-staged contraction core (round 1): dense GEMM, the fused dual-octree GraphConv for the layers the
-// planes kernel (ofx_gemm2.hip) does not take, and the dense-grid 3x3x3 convolution (same kernel, 27 "directions").
+// planes kernel (ofx_gemm2.hip) does not take, and the dense-grid 3x3x3 convolution (same kernels, 27 "directions").
 //
-// One kernel template per contraction precision, two A-tile loaders:
+// Two A-tile modes of the tiled kernels (gemm_pairs_x3_kernel, gemm_fast_kernel):
 //   MODE_DENSE  : A[arow(m), k] row-major (optional row map)                 -> ofx_gemm_f32
-//   MODE_GATHER : A[m, dir*cin + c] = x[nbr[m, dir], c]  (segment mean when a (row,dir)
-//                 has several neighbours), then the dense node-type-fraction slab
-//                                                      -> ofx_graphconv_fwd / ofx_gridconv_fwd
-// The gathered [N, ndir*cin] "col_data" of the reference (modules.py:208-210) never exists
-// in HBM: neighbour rows are fetched (16 B per lane, one 128-B line per 8 lanes) straight
-// into the LDS A-tile.
+//   MODE_GATHER : A[m, dir*cin + c] = x[nbr_ext[m, dir], c] through the extended neighbour table (segments with
+//                 several neighbours are pre-averaged into `aux` rows), then the dense node-type-fraction slab
+//                                     -> ofx_graphconv_fwd / ofx_gridconv_fwd / ofx_gather_gemm_f32 and their backwards
+// The gathered [N, ndir*cin] "col_data" of the reference (modules.py:208-210) never exists in HBM on that path:
+// neighbour rows are fetched (16 B per lane, one 128-B line per 8 lanes) straight into the LDS A-tile.  The gather is
+// branch-free and needs cin % 32 == 0 with 16-B aligned rows; every other gather layer (the input conv with Cin = 3,
+// the VAE decoder's 24-channel convs, a call without the extended table) materialises col_data row chunks in the
+// workspace (col_rows_kernel) and runs MODE_DENSE on them.  gemm_dense_generic_kernel serves only the dense calls the
+// branch-free loader cannot take: K % 4 != 0, lda % 4 != 0 or an A that is not 16-B aligned.
 //
-// Precisions (ofx_set_precision): 0 (default) = bf16x3: both operands split into bf16 hi + lo, three
-// v_mfma_f32_32x32x16_bf16 per product term, fp32 accumulate (gemm_pairs_x3_kernel; ~1e-5 of an fp32 reference);
-// 1 = exact fp32: v_mfma_f32_32x32x2_f32, a k-ordered fma chain (gemm_fast_kernel / gemm_kernel; 157 TF peak).
+// Precisions (ofx_set_precision): 3 (default) = fp16x3: both operands split into fp16 hi + lo, three
+// v_mfma_f32_32x32x16_f16 per product term, fp32 accumulate; 0 / 2 = bf16x3, the same with bf16 pairs (both
+// gemm_pairs_x3_kernel); 1 = exact fp32: v_mfma_f32_32x32x2_f32, a k-ordered fma chain (gemm_fast_kernel; 157 TF peak).
+// gemm_dense_generic_kernel is exact fp32 in every mode.
 // Tiling (wave = 64): block = 4 waves, BM = 128 rows, BK = 32; BN = 128 (2x2 waves of 64x64), 64 (2x2 of 64x32) or
 // 32 (4x1 of 32x32).  Weights are pre-packed once (ofx_pack_weights / ofx_pack_conv3d): fp32 [k/4][n][4] followed by
-// the bf16 hi | lo planes [k/8][n][8].
+// the 16-bit hi | lo planes [k/8][n][8].
 // Small-M problems (dense 4^3 / 8^3 grids) are split along K into up to 64 slices whose
 // partial tiles go to a workspace and are summed, in slice order (deterministic), by
 // splitk_reduce_kernel, which also applies the epilogue.
@@ -27,45 +31,15 @@ constexpr int A_LD = BK + 4;
 constexpr int MODE_DENSE = 0;
 constexpr int MODE_GATHER = 1;
 
-
-// mean over the CSR segment (row, dir) of x[col, cc..cc+3]
-__device__ __forceinline__ float4 gather_seg4(const GemmArgs& g, int64_t row, int dir, int cc) {
-  const int64_t s = row * g.ndir + dir;
-  const int32_t a = g.seg_ptr[s], e = g.seg_ptr[s + 1];
-  float4 acc = f4zero();
-  if (g.edge_w) {
-    for (int32_t p = a; p < e; ++p) {
-      const float w = g.edge_w[p];
-      const float4 v = *reinterpret_cast<const float4*>(g.x + (int64_t)g.col[p] * g.ldx + cc);
-      acc.x += w * v.x; acc.y += w * v.y; acc.z += w * v.z; acc.w += w * v.w;
-    }
-    return acc;
-  }
-  for (int32_t p = a; p < e; ++p) f4add(acc, *reinterpret_cast<const float4*>(g.x + (int64_t)g.col[p] * g.ldx + cc));
-  if (e - a > 1) {
-    const float inv = 1.f / (float)(e - a);
-    acc.x *= inv; acc.y *= inv; acc.z *= inv; acc.w *= inv;
-  }
-  return acc;
-}
-
-// scalar (slow-path) gathered element
-__device__ __forceinline__ float gather_elem(const GemmArgs& g, int64_t row, int64_t k) {
-  if (k >= (int64_t)g.ndir * g.cin) return 0.f;
-  const int dir = (int)(k / g.cin), c = (int)(k - (int64_t)dir * g.cin);
-  const int32_t nb = g.nbr[row * g.ndir + dir];
-  if (nb >= 0) return g.x[(int64_t)nb * g.ldx + c];
-  if (nb == -1) return 0.f;
-  const int64_t s = row * g.ndir + dir;
-  const int32_t a = g.seg_ptr[s], e = g.seg_ptr[s + 1];
-  float acc = 0.f;
-  if (g.edge_w) {
-    for (int32_t p = a; p < e; ++p) acc += g.edge_w[p] * g.x[(int64_t)g.col[p] * g.ldx + c];
-    return acc;
-  }
-  for (int32_t p = a; p < e; ++p) acc += g.x[(int64_t)g.col[p] * g.ldx + c];
-  if (e - a > 1) acc /= (float)(e - a);
-  return acc;
+// this block's k slice and tile (XCD-aware order over all nsplit * ntm * ntn blocks)
+struct TileCoords { int split, tm, tn; };
+__device__ __forceinline__ TileCoords tile_coords(const GemmArgs& g) {
+  const int ntile = g.ntm * g.ntn;
+  int bid = ofx_xcd_swizzle(blockIdx.x, ntile * g.nsplit);
+  const int split = bid / ntile;
+  bid -= split * ntile;
+  const int tm = bid / g.ntn;
+  return {split, tm, bid - tm * g.ntn};
 }
 
 __device__ __forceinline__ void load_a_dense(const GemmArgs& g, int64_t m0, int64_t k0, float4 (&va)[4]) {
@@ -104,29 +78,19 @@ __device__ __forceinline__ void load_b_tile(const GemmArgs& g, int64_t n0, int64
   }
 }
 
-
-
-template <int MODE, int WM, int WN, int MI, int NI>
-__global__ void __launch_bounds__(256, 2) gemm_kernel(const GemmArgs g) {
+// Dense rows the branch-free loader of gemm_fast_kernel cannot take (any K, lda and alignment of A): bounds-checked,
+// scalar where it has to be; exact fp32.
+template <int WM, int WN, int MI, int NI>
+__global__ void __launch_bounds__(256, 2) gemm_dense_generic_kernel(const GemmArgs g) {
   constexpr int BN = WN * NI * 32;
   static_assert(WM * MI * 32 == BM, "BM");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* As = smem;                       // [2][BM * A_LD]
   float* Bs = smem + 2 * BM * A_LD;       // [2][8 * BN * 4]
 
-  // XCD-aware tile order: consecutive tiles (which share gathered neighbour rows through
-  // Morton locality) stay on one XCD / one L2.  Bijective for any grid size.
-  const int ntile = g.ntm * g.ntn;
-  const int nblk = ntile * g.nsplit;
-  int bid = blockIdx.x;
-  {
-    const int q = nblk / 8, r = nblk % 8, xcd = bid % 8, j = bid / 8;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-  }
-  const int split = bid / ntile;
-  bid -= split * ntile;
-  const int tm = bid / g.ntn, tn = bid - tm * g.ntn;
-  const int64_t m0 = (int64_t)tm * BM, n0 = (int64_t)tn * BN;
+  const TileCoords tc = tile_coords(g);
+  const int split = tc.split;
+  const int64_t m0 = (int64_t)tc.tm * BM, n0 = (int64_t)tc.tn * BN;
 
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int wm = wid / WN, wn = wid % WN;
@@ -147,65 +111,6 @@ __global__ void __launch_bounds__(256, 2) gemm_kernel(const GemmArgs g) {
   const int kt_begin = split * g.kt_per_split;
   const int kt_end = (kt_begin + g.kt_per_split < nkt_all) ? kt_begin + g.kt_per_split : nkt_all;
 
-  // gather state: neighbour ids of this thread's 4 rows for the current direction and the next one
-  int32_t nb[4] = {-1, -1, -1, -1}, nbn[4] = {-1, -1, -1, -1};
-  int dir_cur = -1, dir_next = -1;
-  auto load_nbr = [&](int dir, int32_t (&dst)[4]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int64_t m = m0 + r0 + 32 * i;
-      dst[i] = (m < g.M && dir < g.ndir) ? g.nbr[m * g.ndir + dir] : -1;
-    }
-  };
-
-  auto load_a = [&](int kt) {
-    const int64_t k0 = (int64_t)kt * BK;
-    if (MODE == MODE_DENSE) {
-      load_a_dense(g, m0, k0, va);
-    } else if (k0 >= g.Kf) {                               // node-type fraction slab (dense, zero padded)
-      const int64_t kk = k0 - g.Kf + c4 * 4;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int64_t m = m0 + r0 + 32 * i;
-        va[i] = (m < g.M) ? *reinterpret_cast<const float4*>(g.tf + m * g.ldt + kk) : f4zero();
-      }
-    } else if (g.fast) {
-      const int dir = (int)(k0 / g.cin);
-      const int cc = (int)(k0 - (int64_t)dir * g.cin) + c4 * 4;
-      if (dir != dir_cur) {
-        if (dir == dir_next) {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) nb[i] = nbn[i];
-        } else {
-          load_nbr(dir, nb);
-        }
-        dir_cur = dir;
-        dir_next = dir + 1;
-        load_nbr(dir_next, nbn);                             // prefetch: consumed >= cin/32 k-tiles later
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        va[i] = nb[i] >= 0 ? *reinterpret_cast<const float4*>(g.x + (int64_t)nb[i] * g.ldx + cc) : f4zero();
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (nb[i] == -2) va[i] = gather_seg4(g, m0 + r0 + 32 * i, dir, cc);   // several neighbours (rare)
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int64_t m = m0 + r0 + 32 * i;
-        float4 v = f4zero();
-        if (m < g.M) {
-          const int64_t k = k0 + c4 * 4;
-          v.x = gather_elem(g, m, k);
-          v.y = gather_elem(g, m, k + 1);
-          v.z = gather_elem(g, m, k + 2);
-          v.w = gather_elem(g, m, k + 3);
-        }
-        va[i] = v;
-      }
-    }
-  };
-
   auto store_tiles = [&](int buf) {
     float* a = As + buf * BM * A_LD;
 #pragma unroll
@@ -216,7 +121,7 @@ __global__ void __launch_bounds__(256, 2) gemm_kernel(const GemmArgs g) {
   };
 
   if (kt_begin < kt_end) {
-    load_a(kt_begin);
+    load_a_dense(g, m0, (int64_t)kt_begin * BK, va);
     load_b_tile<BN>(g, n0, (int64_t)kt_begin * BK, vb);
     store_tiles(0);
   }
@@ -225,7 +130,7 @@ __global__ void __launch_bounds__(256, 2) gemm_kernel(const GemmArgs g) {
   for (int kt = kt_begin; kt < kt_end; ++kt) {
     const int buf = (kt - kt_begin) & 1;
     if (kt + 1 < kt_end) {
-      load_a(kt + 1);
+      load_a_dense(g, m0, (int64_t)(kt + 1) * BK, va);
       load_b_tile<BN>(g, n0, (int64_t)(kt + 1) * BK, vb);
     }
     const float* a = As + buf * BM * A_LD + (wm * MI * 32 + l31) * A_LD + h * 16;
@@ -258,7 +163,7 @@ __global__ void __launch_bounds__(256, 2) gemm_kernel(const GemmArgs g) {
 // ---------------------------------------------------------------------------------
 // Fast gather kernel: cin % 32 == 0, 16-B aligned rows, extended neighbour table.
 // The loader is branch-free so the compiler keeps the gathers in flight across the MFMA
-// block (the generic kernel's control flow forces s_waitcnt vmcnt(0) before the MFMAs):
+// block (a loader with control flow forces s_waitcnt vmcnt(0) before the MFMAs):
 //   * nbr_ext[m, dir] always names a source row: < n_src -> x, n_src -> the zero row of
 //     `aux` (no neighbour / zero padding), > n_src -> a pre-averaged row of `aux`
 //     (segment with several neighbours, written by multi_mean_kernel);
@@ -334,17 +239,9 @@ __global__ void __launch_bounds__(256, 2) gemm_fast_kernel(const GemmArgs g) {
   float* As = smem;
   float* Bs = smem + 2 * BM * A_LD;
 
-  const int ntile = g.ntm * g.ntn;
-  const int nblk = ntile * g.nsplit;
-  int bid = blockIdx.x;
-  {
-    const int q = nblk / 8, r = nblk % 8, xcd = bid % 8, j = bid / 8;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-  }
-  const int split = bid / ntile;
-  bid -= split * ntile;
-  const int tm = bid / g.ntn, tn = bid - tm * g.ntn;
-  const int64_t m0 = (int64_t)tm * BM, n0 = (int64_t)tn * BN;
+  const TileCoords tc = tile_coords(g);
+  const int split = tc.split;
+  const int64_t m0 = (int64_t)tc.tm * BM, n0 = (int64_t)tc.tn * BN;
 
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int wm = wid / WN, wn = wid % WN;
@@ -412,6 +309,20 @@ __global__ void __launch_bounds__(256, 2) gemm_fast_kernel(const GemmArgs g) {
 
   float4 va0, va1, va2, va3, vb0, vb1, vb2, vb3;
   vb1 = vb2 = vb3 = f4zero();
+  auto load_w = [&](gfp wk) {                          // this thread's float4s of the weight tile at wk
+    vb0 = ldg4(wk + bo0);
+    if (NB > 1) vb1 = ldg4(wk + bo1);
+    if (NB > 2) { vb2 = ldg4(wk + bo2); vb3 = ldg4(wk + bo3); }
+  };
+  auto stage = [&](float* as, float* bs) {             // registers -> the A / B tiles at as / bs
+    *reinterpret_cast<float4*>(as) = va0;
+    *reinterpret_cast<float4*>(as + 32 * A_LD) = va1;
+    *reinterpret_cast<float4*>(as + 64 * A_LD) = va2;
+    *reinterpret_cast<float4*>(as + 96 * A_LD) = va3;
+    *reinterpret_cast<float4*>(bs) = vb0;
+    if (NB > 1) *reinterpret_cast<float4*>(bs + 1024) = vb1;
+    if (NB > 2) { *reinterpret_cast<float4*>(bs + 2048) = vb2; *reinterpret_cast<float4*>(bs + 3072) = vb3; }
+  };
 
   // ------------------------------------------------------------ gather tiles
   if (g_begin < g_end) {
@@ -435,18 +346,9 @@ __global__ void __launch_bounds__(256, 2) gemm_fast_kernel(const GemmArgs g) {
         va3 = ldg4(xp + src_off(ia3, ldx, n_src, aux_delta) + cc);
       }
       const int ktw0 = MODE == MODE_DENSE ? g_begin : d0 * tpd + g_begin / ndir;
-      const gfp wk = wp + (int64_t)ktw0 * 8 * Ncols * 4;
-      vb0 = ldg4(wk + bo0);
-      if (NB > 1) vb1 = ldg4(wk + bo1);
-      if (NB > 2) { vb2 = ldg4(wk + bo2); vb3 = ldg4(wk + bo3); }
+      load_w(wp + (int64_t)ktw0 * 8 * Ncols * 4);
     }
-    *reinterpret_cast<float4*>(a_st) = va0;
-    *reinterpret_cast<float4*>(a_st + 32 * A_LD) = va1;
-    *reinterpret_cast<float4*>(a_st + 64 * A_LD) = va2;
-    *reinterpret_cast<float4*>(a_st + 96 * A_LD) = va3;
-    *reinterpret_cast<float4*>(b_st) = vb0;
-    if (NB > 1) *reinterpret_cast<float4*>(b_st + 1024) = vb1;
-    if (NB > 2) { *reinterpret_cast<float4*>(b_st + 2048) = vb2; *reinterpret_cast<float4*>(b_st + 3072) = vb3; }
+    stage(a_st, b_st);
     ia0 = ib0; ia1 = ib1; ia2 = ib2; ia3 = ib3;
     __syncthreads();
 
@@ -469,24 +371,13 @@ __global__ void __launch_bounds__(256, 2) gemm_fast_kernel(const GemmArgs g) {
         va3 = ldg4(xp + src_off(ia3, ldx, n_src, aux_delta) + cc);
       }
       const int ktw = MODE == MODE_DENSE ? ktn : dn * tpd + ktn / ndir;
-      const gfp wk = wp + (int64_t)ktw * 8 * Ncols * 4;
-      vb0 = ldg4(wk + bo0);
-      if (NB > 1) vb1 = ldg4(wk + bo1);
-      if (NB > 2) { vb2 = ldg4(wk + bo2); vb3 = ldg4(wk + bo3); }
+      load_w(wp + (int64_t)ktw * 8 * Ncols * 4);
       // pin the issue order: hipcc otherwise sinks these loads below the MFMA block (shorter live
       // ranges), which exposes the whole gather latency every k-tile.
       __builtin_amdgcn_sched_barrier(0);
       mfma_tile<WM, WN, MI, NI>(a_ld + buf * BM * A_LD, b_ld + buf * 8 * BN * 4, acc);
       __builtin_amdgcn_sched_barrier(0);
-      float* as = a_st + (buf ^ 1) * BM * A_LD;
-      float* bs = b_st + (buf ^ 1) * 8 * BN * 4;
-      *reinterpret_cast<float4*>(as) = va0;
-      *reinterpret_cast<float4*>(as + 32 * A_LD) = va1;
-      *reinterpret_cast<float4*>(as + 64 * A_LD) = va2;
-      *reinterpret_cast<float4*>(as + 96 * A_LD) = va3;
-      *reinterpret_cast<float4*>(bs) = vb0;
-      if (NB > 1) *reinterpret_cast<float4*>(bs + 1024) = vb1;
-      if (NB > 2) { *reinterpret_cast<float4*>(bs + 2048) = vb2; *reinterpret_cast<float4*>(bs + 3072) = vb3; }
+      stage(a_st + (buf ^ 1) * BM * A_LD, b_st + (buf ^ 1) * 8 * BN * 4);
       ia0 = ib0; ia1 = ib1; ia2 = ib2; ia3 = ib3;
       __syncthreads();
     }
@@ -499,17 +390,8 @@ __global__ void __launch_bounds__(256, 2) gemm_fast_kernel(const GemmArgs g) {
     va1 = ldg4(tfp + m_1 * ldt + cc);
     va2 = ldg4(tfp + m_2 * ldt + cc);
     va3 = ldg4(tfp + m_3 * ldt + cc);
-    const gfp wk = wp + (int64_t)kt * 8 * Ncols * 4;
-    vb0 = ldg4(wk + bo0);
-    if (NB > 1) vb1 = ldg4(wk + bo1);
-    if (NB > 2) { vb2 = ldg4(wk + bo2); vb3 = ldg4(wk + bo3); }
-    *reinterpret_cast<float4*>(a_st) = va0;
-    *reinterpret_cast<float4*>(a_st + 32 * A_LD) = va1;
-    *reinterpret_cast<float4*>(a_st + 64 * A_LD) = va2;
-    *reinterpret_cast<float4*>(a_st + 96 * A_LD) = va3;
-    *reinterpret_cast<float4*>(b_st) = vb0;
-    if (NB > 1) *reinterpret_cast<float4*>(b_st + 1024) = vb1;
-    if (NB > 2) { *reinterpret_cast<float4*>(b_st + 2048) = vb2; *reinterpret_cast<float4*>(b_st + 3072) = vb3; }
+    load_w(wp + (int64_t)kt * 8 * Ncols * 4);
+    stage(a_st, b_st);
     __syncthreads();
     mfma_tile<WM, WN, MI, NI>(a_ld, b_ld, acc);
     __syncthreads();
@@ -534,42 +416,27 @@ typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8h_t __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4h __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ unsigned cvt_pk_bf16(float a, float b) {
-  unsigned r;
-  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-__device__ __forceinline__ void split_bf16x4(const float4& v, uint2& hi, uint2& lo) {
-  hi.x = cvt_pk_bf16(v.x, v.y);
-  hi.y = cvt_pk_bf16(v.z, v.w);
-  const float hx = __uint_as_float(hi.x << 16), hy = __uint_as_float(hi.x & 0xffff0000u);
-  const float hz = __uint_as_float(hi.y << 16), hw = __uint_as_float(hi.y & 0xffff0000u);
-  lo.x = cvt_pk_bf16(v.x - hx, v.y - hy);
-  lo.y = cvt_pk_bf16(v.z - hz, v.w - hw);
-}
 // H16 = 0: bf16 pairs ("bf16x3"); 1: fp16 pairs ("fp16x3": 11 + 11 significand bits, same three MFMAs per product --
 // v_mfma_f32_32x32x16_f16 honours fp16 denormals, so the lo part stays exact down to 2^-24; values beyond the fp16
 // range turn into Inf / NaN, see split16x4).  See ofx_planes.h for the formats.
-__device__ __forceinline__ unsigned cvt_pk_f16(float a, float b) {
-  const _Float16 x = (_Float16)a, y = (_Float16)b;
-  return (unsigned)__builtin_bit_cast(unsigned short, x) | ((unsigned)__builtin_bit_cast(unsigned short, y) << 16);
-}
-__device__ __forceinline__ float f16_lo_f32(unsigned p) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(p & 0xffffu)); }
-__device__ __forceinline__ float f16_hi_f32(unsigned p) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(p >> 16)); }
-__device__ __forceinline__ float sat_f16(float v) { return fminf(fmaxf(v, -65504.f), 65504.f); }
+// Four floats -> their packed hi pairs and lo pairs (g2_split2 with a compile-time mode).
+// fp16 pairs, NO saturation: an operand beyond +-65504 becomes hi = +-Inf, lo = -+Inf, and the products poison the output
+// with NaN -- a loud failure the caller's finiteness check turns into a bf16x3 retry (include/ofx.h, range guard),
+// instead of a silently clamped, plausible-looking result
 template <int H16>
 __device__ __forceinline__ void split16x4(const float4& v, uint2& hi, uint2& lo) {
   if constexpr (H16 == 0) {
-    split_bf16x4(v, hi, lo);
+    hi.x = g2_pk_bf16(v.x, v.y);
+    hi.y = g2_pk_bf16(v.z, v.w);
+    const float hx = g2_bf16_lo(hi.x), hy = g2_bf16_hi(hi.x);
+    const float hz = g2_bf16_lo(hi.y), hw = g2_bf16_hi(hi.y);
+    lo.x = g2_pk_bf16(v.x - hx, v.y - hy);
+    lo.y = g2_pk_bf16(v.z - hz, v.w - hw);
   } else {
-    // NO saturation: an operand beyond +-65504 becomes hi = +-Inf, lo = -+Inf, and the products poison the output
-    // with NaN -- a loud failure the caller's finiteness check turns into a bf16x3 retry (include/ofx.h, range guard),
-    // instead of a silently clamped, plausible-looking result
-    const float x = v.x, y = v.y, z = v.z, w = v.w;
-    hi.x = cvt_pk_f16(x, y);
-    hi.y = cvt_pk_f16(z, w);
-    lo.x = cvt_pk_f16(x - f16_lo_f32(hi.x), y - f16_hi_f32(hi.x));
-    lo.y = cvt_pk_f16(z - f16_lo_f32(hi.y), w - f16_hi_f32(hi.y));
+    hi.x = g2_pk_f16(v.x, v.y);
+    hi.y = g2_pk_f16(v.z, v.w);
+    lo.x = g2_pk_f16(v.x - g2_f16_lo(hi.x), v.y - g2_f16_hi(hi.x));
+    lo.y = g2_pk_f16(v.z - g2_f16_lo(hi.y), v.w - g2_f16_hi(hi.y));
   }
 }
 template <int H16>
@@ -596,17 +463,9 @@ __global__ void __launch_bounds__(256, 2) gemm_pairs_x3_kernel(const GemmArgs g)
   typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
   typedef const u32x4 __attribute__((address_space(1)))* gqp;
 
-  const int ntile = g.ntm * g.ntn;
-  const int nblk = ntile * g.nsplit;
-  int bid = blockIdx.x;
-  {
-    const int q = nblk / 8, r = nblk % 8, xcd = bid % 8, j = bid / 8;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-  }
-  const int split = bid / ntile;
-  bid -= split * ntile;
-  const int tm = bid / g.ntn, tn = bid - tm * g.ntn;
-  const int64_t m0 = (int64_t)tm * BM, n0 = (int64_t)tn * BN;
+  const TileCoords tc = tile_coords(g);
+  const int split = tc.split;
+  const int64_t m0 = (int64_t)tc.tm * BM, n0 = (int64_t)tc.tn * BN;
 
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int wm = wid / WN, wn = wid % WN;
@@ -885,7 +744,7 @@ __global__ void pack_bf16x3_kernel(const float* __restrict__ Wp, int64_t Kp, int
     const int64_t k = kg * 8 + kk;
     const float w = Wp[((k >> 2) * N + n) * 4 + (k & 3)];
     if (h16) {                             // fp16 pairs (precision 3)
-      const float ws = sat_f16(w * wscale);
+      const float ws = g2_sat16(w * wscale);
       const _Float16 hi = (_Float16)ws;
       const _Float16 lo = (_Float16)(ws - (float)hi);
       W16[t] = __builtin_bit_cast(unsigned short, hi);
@@ -1009,44 +868,28 @@ __global__ void __launch_bounds__(256) splitk_reduce_v4_kernel(const GemmArgs g)
   }
 }
 
-template <int MODE, int WM, int WN, int MI, int NI>
-static int launch_cfg(GemmArgs& g, hipStream_t st) {
-  constexpr int BN = WN * NI * 32;
-  constexpr size_t lds = (2 * BM * A_LD + 2 * 8 * BN * 4) * sizeof(float);
+// launch one of the tiled kernels on its ntm * ntn * nsplit grid with LDS bytes of dynamic shared memory
+template <void (*KERNEL)(const GemmArgs), size_t LDS>
+static int launch_tiled(GemmArgs& g, hipStream_t st) {
   static bool attr_set[OFX_MAX_DEVICES] = {};
-  if (lds > 64 * 1024 &&      // e.g. 68 KB for BN = 128: above the 64 KB default cap
-      !ofx_raise_lds_limit(reinterpret_cast<const void*>(&gemm_kernel<MODE, WM, WN, MI, NI>), (int)lds, attr_set))
+  if (LDS > 64 * 1024 &&      // e.g. 68 KB for the fp32 tiles of BN = 128: above the 64 KB default cap
+      !ofx_raise_lds_limit(reinterpret_cast<const void*>(KERNEL), (int)LDS, attr_set))
     return OFX_ELAUNCH;
-  gemm_kernel<MODE, WM, WN, MI, NI><<<g.ntm * g.ntn * g.nsplit, 256, lds, st>>>(g);
+  KERNEL<<<g.ntm * g.ntn * g.nsplit, 256, LDS, st>>>(g);
   return OFX_OK;
 }
-
+// kernel by contraction flavour: 0 = generic dense (exact fp32), 1 = branch-free exact fp32, 2 / 3 = bf16 / fp16 pairs
 template <int MODE, int WM, int WN, int MI, int NI>
-static int launch_fast_cfg(GemmArgs& g, hipStream_t st) {
-  constexpr int BN = WN * NI * 32;
-  constexpr size_t lds = (2 * BM * A_LD + 2 * 8 * BN * 4) * sizeof(float);
-  static bool attr_set[OFX_MAX_DEVICES] = {};
-  if (lds > 64 * 1024 &&      // e.g. 68 KB for BN = 128: above the 64 KB default cap
-      !ofx_raise_lds_limit(reinterpret_cast<const void*>(&gemm_fast_kernel<MODE, WM, WN, MI, NI>), (int)lds, attr_set))
-    return OFX_ELAUNCH;
-  gemm_fast_kernel<MODE, WM, WN, MI, NI><<<g.ntm * g.ntn * g.nsplit, 256, lds, st>>>(g);
-  return OFX_OK;
-}
-
-template <int MODE, int WM, int WN, int MI, int NI, int H16>
-static int launch_bf16x3_h(GemmArgs& g, hipStream_t st) {
-  constexpr int BN = WN * NI * 32;
-  constexpr size_t lds = 2 * (2 * BM * 80);
-  static bool attr_set[OFX_MAX_DEVICES] = {};
-  if (lds > 64 * 1024 &&      // e.g. 68 KB for BN = 128: above the 64 KB default cap
-      !ofx_raise_lds_limit(reinterpret_cast<const void*>(&gemm_pairs_x3_kernel<MODE, WM, WN, MI, NI, H16>), (int)lds, attr_set))
-    return OFX_ELAUNCH;
-  gemm_pairs_x3_kernel<MODE, WM, WN, MI, NI, H16><<<g.ntm * g.ntn * g.nsplit, 256, lds, st>>>(g);
-  return OFX_OK;
-}
-template <int MODE, int WM, int WN, int MI, int NI>
-static int launch_bf16x3_cfg(GemmArgs& g, hipStream_t st) {
-  return g_precision == 3 ? launch_bf16x3_h<MODE, WM, WN, MI, NI, 1>(g, st) : launch_bf16x3_h<MODE, WM, WN, MI, NI, 0>(g, st);
+static int launch_cfg(GemmArgs& g, int flavour, hipStream_t st) {
+  constexpr size_t lds_f32 = (2 * BM * A_LD + 2 * 8 * (WN * NI * 32) * 4) * sizeof(float);
+  constexpr size_t lds_16 = 2 * (2 * BM * 80);
+  switch (flavour) {
+    case 3: return launch_tiled<gemm_pairs_x3_kernel<MODE, WM, WN, MI, NI, 1>, lds_16>(g, st);
+    case 2: return launch_tiled<gemm_pairs_x3_kernel<MODE, WM, WN, MI, NI, 0>, lds_16>(g, st);
+    case 1: return launch_tiled<gemm_fast_kernel<MODE, WM, WN, MI, NI>, lds_f32>(g, st);
+  }
+  if constexpr (MODE == MODE_DENSE) return launch_tiled<gemm_dense_generic_kernel<WM, WN, MI, NI>, lds_f32>(g, st);
+  return OFX_EINVAL;
 }
 
 // second stage of the fused statistics.  Block = 64 consecutive wave rows x 64 columns; thread (rg, c) adds up
@@ -1119,6 +962,9 @@ int ofx_launch_stats_reduce(const GemmArgs& g, int wr_rows, hipStream_t st) {
 template <int MODE>
 static int launch_gemm(GemmArgs& g, float* ws, size_t ws_bytes, hipStream_t st) {
   if (g.M <= 0 || g.N <= 0) return OFX_OK;
+  // gather mode exists only on the branch-free kernels: the entry points send every other layer through
+  // launch_gather_via_col
+  if (MODE == MODE_GATHER && !(g.fast && g.nbr_ext && g.aux && (!g.out_rows || g.gather_out_rows))) return OFX_EINVAL;
   {
     auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     g.vec4 = g.N % 4 == 0 && al16(g.out) && g.ldc % 4 == 0 && (!g.res || (al16(g.res) && g.ldr % 4 == 0)) &&
@@ -1145,11 +991,8 @@ static int launch_gemm(GemmArgs& g, float* ws, size_t ws_bytes, hipStream_t st) 
   nsplit = (int)ofx_cdiv(nkt, g.kt_per_split);
   g.nsplit = nsplit;
   g.ws = ws;
-  int rc;
-  bool fast;
-  if (MODE == MODE_GATHER) {
-    fast = g.fast && g.nbr_ext && g.aux && (!g.out_rows || g.gather_out_rows);
-  } else {
+  bool fast = true;
+  if (MODE == MODE_DENSE) {
     fast = ((g.lda & 3) == 0) && ((g.K & 3) == 0) && g.K >= 4 && ((((uintptr_t)g.A) & 15) == 0);
     if (fast) { g.ndir = 1; g.n_src = 0; g.aux = g.A; g.tf = g.A; g.ldt = g.lda; g.nbr_ext = (const int32_t*)g.A; }
   }
@@ -1161,17 +1004,11 @@ static int launch_gemm(GemmArgs& g, float* ws, size_t ws_bytes, hipStream_t st) 
     g.stats_part = nullptr;
   // the 16-bit halves carry the pack's power-of-two scale; the fp32 pack (exact kernels below) does not
   g.oscale_p = (fast && g.W16) ? g.Wp + 2 * g.Kp * g.N : nullptr;
-  if (fast && g.W16) {
-    if (bn == 32) rc = launch_bf16x3_cfg<MODE, 4, 1, 1, 1>(g, st);
-    else if (bn == 64) rc = launch_bf16x3_cfg<MODE, 2, 2, 2, 1>(g, st);
-    else rc = launch_bf16x3_cfg<MODE, 2, 2, 2, 2>(g, st);
-  } else if (fast) {
-    if (bn == 32) rc = launch_fast_cfg<MODE, 4, 1, 1, 1>(g, st);
-    else if (bn == 64) rc = launch_fast_cfg<MODE, 2, 2, 2, 1>(g, st);
-    else rc = launch_fast_cfg<MODE, 2, 2, 2, 2>(g, st);
-  } else if (bn == 32) rc = launch_cfg<MODE, 4, 1, 1, 1>(g, st);
-  else if (bn == 64) rc = launch_cfg<MODE, 2, 2, 2, 1>(g, st);
-  else rc = launch_cfg<MODE, 2, 2, 2, 2>(g, st);
+  const int flavour = !fast ? 0 : (!g.W16 ? 1 : (g_precision == 3 ? 3 : 2));
+  int rc;
+  if (bn == 32) rc = launch_cfg<MODE, 4, 1, 1, 1>(g, flavour, st);
+  else if (bn == 64) rc = launch_cfg<MODE, 2, 2, 2, 1>(g, flavour, st);
+  else rc = launch_cfg<MODE, 2, 2, 2, 2>(g, flavour, st);
   if (rc) return rc;
   if (nsplit > 1) {
     const bool ws16 = (((uintptr_t)g.ws) & 15) == 0;
@@ -1187,7 +1024,6 @@ static int launch_gemm(GemmArgs& g, float* ws, size_t ws_bytes, hipStream_t st) 
 }
 
 static inline int64_t pad32(int64_t v) { return (v + 31) / 32 * 32; }
-static int pack_bf16x3(const float* Wp, int64_t Kp, int64_t N, hipStream_t st);
 
 extern "C" int64_t ofx_packed_k(int64_t K) { return pad32(K); }
 extern "C" int64_t ofx_graphconv_packed_k(int cin, int nt) {
@@ -1311,9 +1147,27 @@ static int gather_common(GemmArgs& g, const float* x, int64_t ldx, int cin, int 
 }
 
 // Layers the branch-free gather kernel cannot take (Cin not a multiple of 32: the network's input conv with
-// Cin = 3, the VAE decoder's 24/32-channel convs): materialise the reference's col_data rows
+// Cin = 3, the VAE decoder's 24/32-channel convs; no extended table): materialise the reference's col_data rows
 // [rows, Kp] = [7 (27) segment means | node-type slab] into the workspace, one row chunk at a time, and run
 // the dense kernel on them with the same packed weights (their k order is exactly this layout).
+// One gathered element: the neighbour's, the segment mean (weighted sum with edge_w) or zero
+__device__ __forceinline__ float gather_elem(const GemmArgs& g, int64_t row, int64_t k) {
+  if (k >= (int64_t)g.ndir * g.cin) return 0.f;
+  const int dir = (int)(k / g.cin), c = (int)(k - (int64_t)dir * g.cin);
+  const int32_t nb = g.nbr[row * g.ndir + dir];
+  if (nb >= 0) return g.x[(int64_t)nb * g.ldx + c];
+  if (nb == -1) return 0.f;
+  const int64_t s = row * g.ndir + dir;
+  const int32_t a = g.seg_ptr[s], e = g.seg_ptr[s + 1];
+  float acc = 0.f;
+  if (g.edge_w) {
+    for (int32_t p = a; p < e; ++p) acc += g.edge_w[p] * g.x[(int64_t)g.col[p] * g.ldx + c];
+    return acc;
+  }
+  for (int32_t p = a; p < e; ++p) acc += g.x[(int64_t)g.col[p] * g.ldx + c];
+  if (e - a > 1) acc /= (float)(e - a);
+  return acc;
+}
 __global__ void __launch_bounds__(256) col_rows_kernel(const GemmArgs g, int64_t row0, int64_t rows,
                                                        float* __restrict__ colbuf) {
   const int64_t k4n = g.Kp >> 2, total = rows * k4n;
@@ -1328,17 +1182,17 @@ __global__ void __launch_bounds__(256) col_rows_kernel(const GemmArgs g, int64_t
   }
 }
 
-template <int MODE> static int launch_gemm(GemmArgs& g, float* ws, size_t ws_bytes, hipStream_t st);
-
-// returns OFX_OK when it handled the layer, -1 when the workspace is too small (caller uses the generic kernel)
+// The workspace (16-B aligned) is cut into the col rows and a tail of ws_bytes / 8 (at most 16 MB) for the dense kernel's
+// split-K / statistics partials; a workspace without room for 128 col rows is OFX_EINVAL, before any launch
+// (ws_bytes >= 588 * Kp always has it: 7/8 of that is 128 rows of 4 * Kp bytes).
 static int launch_gather_via_col(const GemmArgs& g, float* ws, size_t ws_bytes, hipStream_t st) {
-  if (!ws || (((uintptr_t)ws) & 15)) return -1;
+  if (!ws || (((uintptr_t)ws) & 15)) return OFX_EINVAL;
   size_t tail = ws_bytes / 8;                                  // split-K partials / statistics partials
   if (tail > (size_t(16) << 20)) tail = size_t(16) << 20;
   tail &= ~size_t(15);
   const size_t row_bytes = (size_t)g.Kp * sizeof(float);
   int64_t chunk = (int64_t)((ws_bytes - tail) / row_bytes) / 128 * 128;
-  if (chunk < 128) return -1;
+  if (chunk < 128) return OFX_EINVAL;
   float* tail_ws = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + (ws_bytes - tail));
   for (int64_t r0 = 0; r0 < g.M; r0 += chunk) {
     const int64_t rows = g.M - r0 < chunk ? g.M - r0 : chunk;
@@ -1379,20 +1233,17 @@ extern "C" int ofx_graphconv_fwd(const float* x, int64_t ldx, int cin, int64_t n
     ws = nullptr;                              // fused statistics need the single-pass epilogue (no split-K)
   }
   hipStream_t st = ofx_stream(stream);
-  if (g.fast && nbr_ext && aux && n_nodes > 0 && (((uintptr_t)aux & 15) == 0)) {
+  if (g.fast && nbr_ext && aux && (((uintptr_t)aux & 15) == 0)) {
     if (n_multi < 0 || (n_multi > 0 && !multi_seg)) return OFX_EINVAL;
     // pre-pass: zero row + mean rows of the (few) segments with several neighbours
     multi_mean_kernel<<<ofx_grid((n_multi + 1) * (cin / 4), 256), 256, 0, st>>>(x, ldx, cin, seg_ptr, col, multi_seg,
                                                                                n_multi, aux, ldx, nullptr);
     g.nbr_ext = nbr_ext; g.aux = aux; g.ldaux = ldx; g.n_src = n_nodes;
     if (!g.tf) { g.tf = x; g.ldt = ldx; }       // never dereferenced past the gather tiles; keeps selects defined
+    return launch_gemm<MODE_GATHER>(g, (float*)ws, ws_bytes, st);
   }
-  if (!g.nbr_ext && n_nodes > 0) {
-    // stats set `ws` aside for the partial sums: the col path manages the whole workspace itself
-    rc = launch_gather_via_col(g, stats ? g.stats_part : (float*)ws, stats ? g.stats_part_bytes : ws_bytes, st);
-    if (rc >= 0) return rc;
-  }
-  return launch_gemm<MODE_GATHER>(g, (float*)ws, ws_bytes, st);
+  // stats set `ws` aside for the partial sums: the col path manages the whole workspace itself
+  return launch_gather_via_col(g, stats ? g.stats_part : (float*)ws, stats ? g.stats_part_bytes : ws_bytes, st);
 }
 
 // Backward of GraphConv with respect to its input (autograd of modules.py:205-213 + :213's matmul):
@@ -1412,19 +1263,16 @@ extern "C" int ofx_graphconv_bwd_data(const float* dy, int64_t ldy, int cout, in
   if (rc) return rc;
   if (!rev_ptr || !rev_row || !rev_w || KpT != g.Kf) return OFX_EINVAL;
   g.edge_w = rev_w;
+  g.tf = dy; g.ldt = ldy;                         // no type slab (Kp == Kf): never dereferenced
   hipStream_t st = ofx_stream(stream);
   if (g.fast && nbr_ext_rev && aux && (((uintptr_t)aux & 15) == 0)) {
     if (n_multi < 0 || (n_multi > 0 && !multi_seg)) return OFX_EINVAL;
     multi_mean_kernel<<<ofx_grid((n_multi + 1) * (cout / 4), 256), 256, 0, st>>>(dy, ldy, cout, rev_ptr, rev_row,
                                                                                 multi_seg, n_multi, aux, ldy, rev_w);
     g.nbr_ext = nbr_ext_rev; g.aux = aux; g.ldaux = ldy; g.n_src = n_nodes;
-    g.tf = dy; g.ldt = ldy;
-  } else {
-    g.tf = dy; g.ldt = ldy;                       // col path: no type slab (Kp == Kf), never dereferenced
-    rc = launch_gather_via_col(g, (float*)ws, ws_bytes, st);
-    if (rc >= 0) return rc;
+    return launch_gemm<MODE_GATHER>(g, (float*)ws, ws_bytes, st);
   }
-  return launch_gemm<MODE_GATHER>(g, (float*)ws, ws_bytes, st);
+  return launch_gather_via_col(g, (float*)ws, ws_bytes, st);
 }
 
 // ---------------------------------------------------------------------------------
@@ -1521,10 +1369,10 @@ __global__ void __launch_bounds__(256, 2) tn_gemm_kernel(const TnArgs a) {
         quad_transpose(w.x, w.y, w.z, w.w, b0, b1);
         const int col = 4 * (f0 + 8 * p) + q4;
         uint2 hi, lo;
-        split_bf16x4(v, hi, lo);
+        split16x4<0>(v, hi, lo);
         *reinterpret_cast<uint2*>(Pt + col * 80 + kg * 8) = hi;
         *reinterpret_cast<uint2*>(Pt + col * 80 + kg * 8 + TP) = lo;
-        split_bf16x4(w, hi, lo);
+        split16x4<0>(w, hi, lo);
         *reinterpret_cast<uint2*>(Qt + col * 80 + kg * 8) = hi;
         *reinterpret_cast<uint2*>(Qt + col * 80 + kg * 8 + TP) = lo;
       }
@@ -1708,11 +1556,9 @@ extern "C" int ofx_gridconv_bwd_data(const float* dy, int64_t ldy, int cout, int
     multi_mean_kernel<<<ofx_grid((n_multi + 1) * (cout / 4), 256), 256, 0, st>>>(dy, ldy, cout, rev_ptr, rev_row,
                                                                                 multi_seg, n_multi, aux, ldy, rev_w);
     g.nbr_ext = nbr_ext_rev; g.aux = aux; g.ldaux = ldy; g.n_src = n_out;
-  } else {
-    rc = launch_gather_via_col(g, (float*)ws, ws_bytes, st);
-    if (rc >= 0) return rc;
+    return launch_gemm<MODE_GATHER>(g, (float*)ws, ws_bytes, st);
   }
-  return launch_gemm<MODE_GATHER>(g, (float*)ws, ws_bytes, st);
+  return launch_gather_via_col(g, (float*)ws, ws_bytes, st);
 }
 
 extern "C" int ofx_gridconv_bwd_weight(const float* x, int64_t ldx, int cin, int64_t n_in, int64_t n_out,
@@ -1818,14 +1664,10 @@ extern "C" int ofx_gridconv_fwd(const float* x, int64_t ldx, int cin, int64_t n_
   if (g.fast && nbr27_ext && zero_row && (((uintptr_t)zero_row & 15) == 0)) {
     g.nbr_ext = nbr27_ext; g.aux = zero_row; g.ldaux = ldx; g.n_src = n_in;   // padded taps name row n_in = zero row
     g.tf = x; g.ldt = ldx;
-  } else if (!nbr27) {
-    return OFX_EINVAL;            // generic path needs the -1-padded table
+    return launch_gemm<MODE_GATHER>(g, (float*)ws, ws_bytes, ofx_stream(stream));
   }
-  if (!g.nbr_ext) {
-    rc = launch_gather_via_col(g, (float*)ws, ws_bytes, ofx_stream(stream));
-    if (rc >= 0) return rc;
-  }
-  return launch_gemm<MODE_GATHER>(g, (float*)ws, ws_bytes, ofx_stream(stream));
+  if (!nbr27) return OFX_EINVAL;  // the col path needs the -1-padded table
+  return launch_gather_via_col(g, (float*)ws, ws_bytes, ofx_stream(stream));
 }
 
 // out[orow(r), :] = [ x[tab[r, 0], :] | ... | x[tab[r, ntap - 1], :] ] @ W + bias + res[r]: the branch-free gather-GEMM with

@@ -40,11 +40,7 @@ __global__ void __launch_bounds__(512, 2) gconv2_kernel(const Gemm2Args a) {   /
   float osc = *g.oscale_p;            // epilogue scale (ofx_planes.h), read here: no scalar load near the k-loop's waits
   asm volatile("" : "+s"(osc));
   const int ntile = g.ntm * g.ntn;
-  int bid = blockIdx.x;
-  {   // XCD-aware bijective tile order: consecutive row tiles (Morton neighbours) share one XCD's L2
-    const int q = ntile / 8, r = ntile % 8, xcd = bid % 8, j = bid / 8;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-  }
+  const int bid = ofx_xcd_swizzle(blockIdx.x, ntile);   // consecutive row tiles (Morton neighbours) share one XCD's L2
   const int tm = bid / g.ntn, tn = bid - tm * g.ntn;
   const int64_t m0 = a.row0 + (int64_t)tm * G2_BM, n0 = (int64_t)tn * G2_BN;
 
@@ -107,8 +103,7 @@ __global__ void __launch_bounds__(512, 2) gconv2_kernel(const Gemm2Args a) {   /
   if (wid == 0) {
     int nb = (int)blockIdx.x + a.prefetch;
     if (nb < ntile) {
-      const int q = ntile / 8, r = ntile % 8, xcd = nb % 8, j = nb / 8;
-      nb = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
+      nb = ofx_xcd_swizzle(nb, ntile);
       const int64_t m2 = a.row0 + (int64_t)(nb / g.ntn) * G2_BM;
       gcp p = (gcp)(a.nbr_ext + m2 * 7) + lane * 128;
       gcp last = (gcp)(a.nbr_ext + g.M * 7) - 4;

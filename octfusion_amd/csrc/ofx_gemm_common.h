@@ -130,6 +130,14 @@ __device__ __forceinline__ void ofx_store_planes4(float* base, int64_t f, const 
   *reinterpret_cast<uint2*>(o + 64) = make_uint2(l0, l1);
 }
 
+// XCD-aware tile order: the dispatcher deals consecutive block ids round-robin to the 8 XCDs, so block `bid` of `n`
+// takes the tile whose index keeps consecutive tiles (which share gathered neighbour rows through Morton locality) on
+// one XCD / one L2.  Bijective on [0, n) for any n.
+__device__ __forceinline__ int ofx_xcd_swizzle(int bid, int n) {
+  const int q = n / 8, r = n % 8, xcd = bid % 8, j = bid / 8;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
+}
+
 __device__ __forceinline__ float4 f4zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 __device__ __forceinline__ void f4add(float4& a, const float4& b) { a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w; }
 

@@ -484,6 +484,97 @@ def test_gemm_tn_rows_strides_and_small_workspaces():
     assert cases == 10
 
 
+def _col_ws_cases(name, run, ref64, out_shape, Kp, ws):
+    """The workspace contract of the col path (include/ofx.h): run(ws, ws_bytes, out) with (i) the full workspace and
+    (ii) exactly the documented sufficient 588 * Kp bytes matches float64; (iii) no workspace and (iv) 128 col rows
+    without their tail are OFX_EINVAL argument checks that leave `out` alone."""
+    from octfusion_amd import _lib
+    for nbytes in (ws.numel(), 588 * Kp):
+        out = torch.full(out_shape, 7.0, device=dev())
+        run(ws, nbytes, out)
+        e = _rel(out, ref64)
+        report(dict(test='col_path_workspace', path=name, ws_bytes=nbytes, rel_to_max=e))
+        assert e <= 5e-5, (name, nbytes, e)
+    for w, nbytes in ((None, 0), (None, ws.numel()), (ws, 512 * Kp)):
+        out = torch.full(out_shape, 7.0, device=dev())
+        with pytest.raises(_lib.OfxError, match=name.split(' ')[0]):
+            run(w, nbytes, out)
+        torch.cuda.synchronize()
+        assert bool((out == 7.0).all()), (name, nbytes)
+
+
+def test_col_path_workspace_contract():
+    """ofx_graphconv_fwd, ofx_graphconv_bwd_data and ofx_gridconv_fwd on layers the branch-free kernel cannot take:
+    the workspace is required (there is no in-kernel gather behind it), 588 * Kp bytes are enough, and the table path
+    (cin % 32 == 0 with nbr_ext) still needs none."""
+    import torch.nn.functional as F
+    from octfusion_amd import _lib, graph_unet_lr as LR, ops
+    from octfusion_amd._lib import call, ptr, stream
+    doc, o_doc = _small_tree()
+    d = 4
+    seg_ptr, col, N, E = doc.csr(d)
+    assert N > 256 and N % 128 != 0                                        # many 128-row chunks and a ragged one
+    ws = ops.workspace(dev())
+    cout = 32
+    A = _seg_mean_matrix(o_doc, d, N, torch.float64)
+    nbr_ext, multi_seg, V = doc.ext(d)
+
+    def fwd(x, pw, cin, table, w, nbytes, out):
+        aux = torch.empty((V + 1) * cin, dtype=torch.float32, device=dev()) if table else None
+        call('ofx_graphconv_fwd', ptr(x), cin, cin, N, ptr(doc.nbr(d)), ptr(seg_ptr), ptr(col),
+             ptr(nbr_ext) if table else None, ptr(multi_seg) if table else None, V if table else 0, ptr(aux), None, 0, 0,
+             ptr(pw.t), pw.Kp, cout, None, None, 0, None, None, 0, ptr(out), cout, None, cout, ptr(w), nbytes, stream())
+
+    for cin in (3, 24, 64):
+        x = C.rand_input('cwx%d' % cin, N, cin)
+        W = _weights('cww%d' % cin, cin, 0, cout)
+        ref = torch.sparse.mm(A, x.double()).view(N, 7 * cin) @ W.double()
+        xg = x.to(dev())
+        pw = ops.PackedWeight().get(W.to(dev()), 'graphconv', cin, 0)
+        if cin == 64:                                                      # table path: never needed the workspace
+            out = torch.full((N, cout), 7.0, device=dev())
+            fwd(xg, pw, cin, True, None, 0, out)
+            assert _rel(out, ref) <= 5e-5
+        else:
+            _col_ws_cases('ofx_graphconv_fwd cin=%d' % cin, lambda w, nb, out: fwd(xg, pw, cin, False, w, nb, out), ref,
+                          (N, cout), pw.Kp, ws)
+
+    # dx of the same layers: the gathered operand is dy.  No reverse table for the layers of the forward cases; with
+    # one, a dy of 24 channels still takes the col path
+    rv = doc.rev(d)
+    for cin, co, table in ((3, 32, False), (24, 32, False), (32, 24, True)):
+        dy = C.rand_input('cwdy%d_%d' % (cin, co), N, co)
+        W = _weights('cwbw%d_%d' % (cin, co), cin, 0, co)
+        ref = _gconv_dx_ref(o_doc, d, dy, W, cin, 0, torch.float64)
+        dyg = dy.to(dev())
+        wt = W.view(7, cin, co).permute(0, 2, 1).reshape(7 * co, cin).contiguous().to(dev())
+        pwt = ops.PackedWeight().get(wt, 'graphconv', co, 0)
+
+        def bwd(w, nbytes, out, dyg=dyg, pwt=pwt, cin=cin, co=co, table=table):
+            call('ofx_graphconv_bwd_data', ptr(dyg), co, co, N, ptr(rv['nbr']), ptr(rv['rev_ptr']), ptr(rv['rev_row']),
+                 ptr(rv['rev_w']), ptr(rv['nbr_ext']) if table else None, ptr(rv['multi_seg']) if table else None,
+                 rv['V'] if table else 0, None, ptr(pwt.t), pwt.Kp, cin, ptr(out), cin, ptr(w), nbytes, stream())
+        _col_ws_cases('ofx_graphconv_bwd_data cin=%d cout=%d' % (cin, co), bwd, ref, (N, cin), pwt.Kp, ws)
+
+    # 4^3 grid, 3 -> 32 channels
+    B, gd, cin = 3, 2, 3
+    S, n = 1 << gd, B * 8 ** gd
+    x = C.rand_input('cwgx', B, cin, S, S, S)
+    wgt = C.rand_input('cwgw', cout, cin, 3, 3, 3) * (1.5 / math.sqrt(27 * cin))
+    ref = F.conv3d(x.double(), wgt.double(), None, padding=1)
+    gs = LR.GridState(B, gd, dev())
+    xr = ops.voxel2octree_cf(x.to(dev()).contiguous(), gd)
+    pc = ops.PackedConv3d().get(wgt.to(dev()))
+    Kp = _lib.lib().ofx_conv3d_packed_k(cin)
+
+    def grid(w, nbytes, out):
+        call('ofx_gridconv_fwd', ptr(xr), xr.stride(0), cin, n, n, ptr(gs.cache.table(0, gd, False)), None,
+             ptr(ops.zero_row(dev())), ptr(pc.t), cout, None, None, 0, None, None, 0, ptr(out), cout, ptr(w), nbytes,
+             stream())
+    # (the float64 oracle rounded to fp32 on its way through the row layout: 2^-24, far below the bound)
+    _col_ws_cases('ofx_gridconv_fwd cin=3', grid, ops.voxel2octree_cf(ref.float().to(dev()).contiguous(), gd), (n, cout), Kp, ws)
+
+
 # =============================================================================================================== C
 def _check_reverse_tables(doc, o_doc, d):
     """doc.rev(d) against the host construction of test_graphconv_backward_vs_autograd; returns (non-empty reverse
