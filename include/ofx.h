@@ -737,6 +737,35 @@ int ofx_mesh_cc_extract(const float* verts, const int32_t* faces, const int64_t*
                         const int64_t* new_tri_off, float* out_verts, int32_t* out_faces, void* ws,
                         const int32_t* status, void* stream);
 
+/* ------------------------------------------------------------------ voxel meshes of octrees (csrc/ofx_voxmesh.hip)
+ * The octree export of the generate path (export_octree, octfusion_model_union.py:403-422: the nodes of one depth
+ * scattered into a dense float grid, then voxel2mesh / _voxel2mesh, ldm_diffusion_util.py:345-446, a Python loop over
+ * the occupied voxels): one quad, as two triangles, for every face of an occupied cell whose neighbour is empty or
+ * outside the grid.  tests/voxmesh_oracle.py restates the output with numpy.
+ * Occupancy: R = 2^depth, 1 <= depth <= 9; one bitmask per shape, cell (x, y, z) = bit (x*R + y)*R + z (x slowest, the
+ * order of np.where), kept in the workspace.  Two calls fill it:
+ * ofx_voxmesh_mask_keys: clears the mask, then sets the cell of every key (int64 [n], what Octree.key(depth) holds:
+ *   Morton code of depth levels, batch id from bit 48) whose batch id lies in [batch0, batch0 + batch).
+ * ofx_voxmesh_mask_dense: occ [batch, R, R, R] fp32; a cell is occupied iff its value is finite and > threshold (a
+ *   neighbour EQUAL to the threshold counts as empty; the reference emits no face toward it).
+ * ofx_voxmesh_count: counts[b*2 + {0,1}] = quads, welded vertices (0 when !weld) of shape b (int64).  A shape has
+ *   2 * quads triangles and, unwelded, 4 * quads vertices.
+ * ofx_voxmesh_emit: after the caller has read the counts back, writes shape b's vertices at verts + 3 * vert_off[b]
+ *   and its triangles at faces + 3 * tri_off[b] (offsets: int64 device arrays), int32 indices into the shape's own
+ *   vertices.  Quads in ascending cell order, within a cell +z, -z, -x, +x, +y, -y, each with the reference's corner
+ *   order and triangle pair (all wound outward).  Unwelded (the reference's arrays verbatim): four vertices per quad
+ *   in its corner order.  Welded: every lattice corner a quad uses once, in ascending corner index
+ *   (cx*(R+1) + cy)*(R+1) + cz.  Coordinates corner * (2 / R) - 1, exact in fp32.
+ * Output is bitwise reproducible (popcounts and scans; the only atomics are the ORs into the bitmasks).  `weld` must be
+ * the same for ws_bytes, count and emit.  Limits: batch * R^3 * 24 <= INT32_MAX (ofx_voxmesh_ws_bytes returns 0
+ * outside, which excludes depth 9). */
+size_t ofx_voxmesh_ws_bytes(int batch, int depth, int weld);
+int ofx_voxmesh_mask_keys(const int64_t* keys, int64_t n, int batch0, int batch, int depth, void* ws, void* stream);
+int ofx_voxmesh_mask_dense(const float* occ, int batch, int depth, float threshold, void* ws, void* stream);
+int ofx_voxmesh_count(int batch, int depth, int weld, void* ws, int64_t* counts, void* stream);
+int ofx_voxmesh_emit(int batch, int depth, int weld, void* ws, const int64_t* vert_off, const int64_t* tri_off,
+                     float* verts, int32_t* faces, void* stream);
+
 /* ------------------------------------------------------------------ evaluation metrics (csrc/ofx_metrics.hip)
  * The reference's metrics/ package (generate_pointclouds.py:14-37, evaluation_metrics.py:111-201, the CUDA extension
  * pytorch_structural_losses: nndistance.cu, approxmatch.cu:3-224).  Point clouds are [N, n, 3] fp32, the reference's

@@ -160,6 +160,11 @@ _SIGS = {
     'ofx_mesh_cc_stats': (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_l, c_l, c_l, c_p, c_p, c_p, c_p], True),
     'ofx_mesh_cc_select': (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_l, c_l, c_p, c_p, c_p, c_p, c_p], True),
     'ofx_mesh_cc_extract': (c_i, [c_p, c_p, c_p, c_p, c_i, c_l, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_p], True),
+    'ofx_voxmesh_ws_bytes': (c_sz, [c_i, c_i, c_i], False),
+    'ofx_voxmesh_mask_keys': (c_i, [c_p, c_l, c_i, c_i, c_i, c_p, c_p], True),
+    'ofx_voxmesh_mask_dense': (c_i, [c_p, c_i, c_i, c_f, c_p, c_p], True),
+    'ofx_voxmesh_count': (c_i, [c_i, c_i, c_i, c_p, c_p, c_p], True),
+    'ofx_voxmesh_emit': (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p], True),
     'ofx_surface_sample_ws_bytes':(c_sz, [c_i, c_l], False),
     'ofx_surface_sample': (c_i, [c_p, c_p, c_p, c_p, c_i, c_l, c_i, c_u64, c_i, c_p, c_p, c_p], True),
     'ofx_nn_matrix': (c_i, [c_p, c_l, c_i, c_p, c_l, c_i, c_p, c_p], True),

@@ -18,6 +18,7 @@ mesh.py lists the differences).
     python -m octfusion_amd.generate --config snet_uncond --shapes 8 --mesh --out samples     # + samples/<i>.obj
     python -m octfusion_amd.generate --config snet_uncond --shapes 8 --mesh --points 2048 --out samples  # + <i>.npy
     python -m octfusion_amd.generate --config snet_uncond --shapes 8 --mesh --clean --out samples   # largest component
+    python -m octfusion_amd.generate --config snet_uncond --shapes 8 --no-vae --octree-mesh --out samples
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \\
         -m octfusion_amd.generate --config snet_cond --shapes 32 --category 2
 """
@@ -79,13 +80,14 @@ def prepare(config, rank, device, ckpt=None, vae_ckpt=None, with_vae=True, allow
 
 def generate(net, cfg, n_shapes, rank, world, seed=0, ddim_steps=200, label=None, vae=None, out_dir=None,
              shapes_per_call=1, use_graph=None, sdf_resolution=None, timings=None, mesh=False, mesh_level=0.0,
-             mesh_scale=1.0, points=None, mesh_clean=False):
+             mesh_scale=1.0, points=None, mesh_clean=False, octree_mesh=False):
     """Yields (result indices, output dict, seconds) for every group of shapes this rank owns.  mesh: also
     out['meshes'] (needs the VAE and sdf_resolution), written as <out_dir>/<index>.obj.  points (needs mesh): also
     out['points'] = {position in the group: [points, 3] cloud} of every non-empty mesh, sampled on the device after the
     unit-cube normalisation (metrics.sample_surface keyed by the result index), written as <out_dir>/<index>.npy.
     mesh_clean (needs mesh): the meshes, files and clouds are those of each shape's largest component, and
-    out['mesh_components'] holds the component counts before cleaning."""
+    out['mesh_components'] holds the component counts before cleaning.  octree_mesh: also out['octree_meshes'] (and
+    out['octree_meshes_large'] for a 3-stage config), written as <out_dir>/octree/<index>.obj (octree_large/)."""
     if mesh_clean and not mesh:
         raise ValueError('mesh_clean needs mesh')
     cs = CascadeSampler(net, cfg, vae)
@@ -100,7 +102,8 @@ def generate(net, cfg, n_shapes, rank, world, seed=0, ddim_steps=200, label=None
         out = cs.sample(len(idxs), ddim_steps=ddim_steps, label=lab, seed=seed, shape_indices=idxs,
                         use_graph=use_graph, sdf_resolution=sdf_resolution if vae is not None else None,
                         timings=timings, mesh=mesh, mesh_level=mesh_level, mesh_scale=mesh_scale,
-                        **({'mesh_clean': True} if mesh_clean else {}))
+                        **({'mesh_clean': True} if mesh_clean else {}),
+                        **({'octree_mesh': True} if octree_mesh else {}))
         if dev.type == 'cuda':
             torch.cuda.synchronize()
             from . import ops
@@ -128,7 +131,10 @@ def write_outputs(out_dir, idxs, out, cfg):
     """Per shape: <index>/split_small.pth (+ split_large.pth) in the reference's sample-file format
     (tools/gen_split.py:50-54), <index>/sdf.pt when the SDF lattice was computed, and <index>.obj (export_mesh's
     file name, octfusion_model_union.py:466) when the meshes were -- an empty mesh is skipped with a warning -- and
-    <index>.npy, its [points, 3] surface samples, when they were."""
+    <index>.npy, its [points, 3] surface samples, when they were.  With the octree meshes: octree/<index>.obj
+    (export_octree's file name, :376,420) and, for the large depth, octree_large/<index>.obj -- the reference writes
+    both depths to octree/<index>.obj, so its depth-8 file replaces the depth-6 one
+    (octfusion_model_union_3t.py:172,191)."""
     from .octree import octree2split_large, octree2split_small
     small = octree2split_small(out['octree_small'], cfg['full_depth'])
     large = bid = None
@@ -149,6 +155,10 @@ def write_outputs(out_dir, idxs, out, cfg):
         if 'meshes' in out:
             from . import mesh
             mesh.write_obj(os.path.join(out_dir, '%d.obj' % i), *out['meshes'][b])
+        for key, sub in (('octree_meshes', 'octree'), ('octree_meshes_large', 'octree_large')):
+            if key in out:
+                from . import mesh
+                mesh.write_obj(os.path.join(out_dir, sub, '%d.obj' % i), *out[key][b])
         if b in out.get('points', {}):
             np.save(os.path.join(out_dir, '%d.npy' % i), out['points'][b].cpu().numpy())
 
@@ -180,6 +190,10 @@ def run(args, rank, local_rank, world, device):
     kw = dict(mesh=True, mesh_level=args.mesh_level, mesh_scale=mesh_scale(args.config), points=points) if mesh else {}
     if clean:
         kw['mesh_clean'] = True
+    if getattr(args, 'octree_mesh', False):
+        if not args.out:
+            raise ValueError('--octree-mesh needs --out')
+        kw['octree_mesh'] = True
     for idxs, out, dt in generate(net, cfg, args.shapes, rank, world, args.seed, args.steps, label, vae, args.out, batch,
                                   sdf_resolution=args.sdf_resolution, timings=timings, **kw):
         done.append((idxs, dt))
@@ -227,9 +241,15 @@ def main(argv=None):
                     help='with --mesh: keep only the largest connected component of every mesh (the reference\'s '
                          'export_mesh clean=True); the .obj, the --points cloud and the vertex / face counts are the '
                          'cleaned mesh\'s, and the result line gains rank0_mesh_components (counts before cleaning)')
+    ap.add_argument('--octree-mesh', action='store_true',
+                    help='write the generated octree itself as a mesh of cubes, <out>/octree/<index>.obj (the '
+                         'reference\'s export_octree) and, for a three-stage config, <out>/octree_large/<index>.obj; '
+                         'needs --out, works with --no-vae')
     args = ap.parse_args(argv)
     if args.clean and not args.mesh:
         raise ValueError('--clean needs --mesh')
+    if args.octree_mesh and not args.out:
+        raise ValueError('--octree-mesh needs --out')
     rank, local_rank, world = dist.init()
     from . import _lib
     _lib.require_device()

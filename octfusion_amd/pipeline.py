@@ -11,6 +11,8 @@ for 3), on device, for a whole batch of independent shapes.
 
     sdf  : NeuralMPU sweep of the decoded field on the resolution^3 lattice in [-sdf_scale, sdf_scale]^3
            (get_sdfs, octfusion_model_union.py:425-433) -- one kernel launch per shape.
+    octree mesh : (opt-in) the cubes of the octree after each split stage as a mesh (voxmesh.octree_mesh;
+           export_octree, octfusion_model_union.py:403-422, a Python loop over a dense grid on the host).
     mesh : (opt-in) marching cubes of every lattice on device (mesh.marching_cubes; export_mesh,
            octfusion_model_union.py:435-468, runs skimage on the host), with mesh_clean only the largest component
            of each (clean=True, :459-467).
@@ -132,7 +134,7 @@ class CascadeSampler:
 
     def _sample_once(self, batch_size, ddim_steps=200, label=None, split_small=None, noises=None, sdf_resolution=None,
                      sdf_scale=0.9, use_graph=None, seed=None, save_index=0, shape_indices=None, timings=None,
-                     mesh=False, mesh_level=0.0, mesh_scale=1.0, mesh_clean=False):
+                     mesh=False, mesh_level=0.0, mesh_scale=1.0, mesh_clean=False, octree_mesh=False):
         """Returns a dict with the per-stage results.  `noises` (optional) = dict of explicit
         init / step noise tensors per stage for reproducible runs.  sdf_resolution (e.g. 256) adds
         out['sdfs'] [B, R, R, R] (needs the VAE).
@@ -148,7 +150,10 @@ class CascadeSampler:
         reference's point_scale); one host sync for the count readback.
         mesh_clean: keep only each mesh's largest component (the reference's sample(clean=), export_mesh
         clean=True, octfusion_model_union.py:459-467) and add out['mesh_components'], the component counts before
-        cleaning; one more host sync (the kept counts)."""
+        cleaning; one more host sync (the kept counts).
+        octree_mesh: also out['octree_meshes'] = per-shape (verts, faces) of the cubes of every node at the small depth
+        (voxmesh.octree_mesh; the reference's export_octree, :376,403-422) and, for a 3-stage model,
+        out['octree_meshes_large'] at the large depth (octfusion_model_union_3t.py:191); one host sync each."""
         import time as _time
         noises = dict(noises or {})
         out = {}
@@ -183,6 +188,11 @@ class CascadeSampler:
         out['split_small'] = split_small
         octree = split2octree_small(split_small, self.depths[1], self.full_depth)
         out['octree_small'] = octree
+        if octree_mesh:
+            from . import voxmesh as _voxmesh
+            t0 = lap('octree_and_graph', t0)
+            out['octree_meshes'] = _voxmesh.octree_mesh(octree, self.depths[1])
+            t0 = lap('octree_mesh', t0)
         if len(self.stages) < 2:
             return out
         doctree = DualOctree(octree)
@@ -208,6 +218,10 @@ class CascadeSampler:
             split_large = x[x.shape[0] - nn6:].contiguous()
             octree = split2octree_large(octree, split_large, self.depths[1])
             out['octree_large'] = octree
+            if octree_mesh:
+                t0 = lap('octree_and_graph', t0)
+                out['octree_meshes_large'] = _voxmesh.octree_mesh(octree, self.depths[2])
+                t0 = lap('octree_mesh', t0)
             doctree = DualOctree(octree)
             t0 = lap('octree_and_graph', t0)
             if gens is not None and 'feature' not in noises:
