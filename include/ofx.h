@@ -494,7 +494,10 @@ int ofx_gn_apply_planes(const float* x, int64_t ldx, int64_t n, int C, const int
  *   left_src  int32: the source rows of the leftover aux rows, flattened (the CSR segment of each, in order).
  * Leftover rows are re-normalised from x by extra blocks interleaved with the main blocks.  mean / rstd from
  * ofx_gn_finalize, or both NULL with (sums, count, groups, eps, count_eps): finalised per block on the fly, as in
- * ofx_gn_apply.  out must not alias x.  Host-side builder: octfusion_amd/dual_octree.py DualOctree.oct_plan. */
+ * ofx_gn_apply -- for C / groups >= 2 only: a block that holds rows of a third batch element derives that element's
+ * statistics assuming four consecutive channels span at most two groups, so C == groups without mean / rstd is
+ * OFX_EINVAL (call ofx_gn_finalize first and pass its mean / rstd).  out must not alias x.  Host-side builder:
+ * octfusion_amd/dual_octree.py DualOctree.oct_plan. */
 int ofx_gn_apply_planes_oct(const float* x, int64_t ldx, int64_t n, int C, const int32_t* batch_id, const float* mean,
                             const float* rstd, const double* sums, const float* count, int groups, float eps,
                             float count_eps, const float* w, const float* bias, int act, int mode, void* out,

@@ -697,7 +697,9 @@ __global__ void __launch_bounds__(256) gn_apply_oct_kernel(const float* __restri
         m = *reinterpret_cast<const float4*>(fin_ms + (slot * 2 + 0) * 1024 + c);
         rs = *reinterpret_cast<const float4*>(fin_ms + (slot * 2 + 1) * 1024 + c);
       } else {                                            // (tiny graph levels: a third batch element inside one block)
-        // four consecutive channels lie in at most two groups (channels per group >= 2): first and last channel's
+        // four consecutive channels lie in at most two groups: first and last channel's.  True for channels per group
+        // >= 2 only -- ofx_gn_apply_planes_oct refuses C == groups without mean / rstd (the per-channel form of
+        // gn_apply_kernel costs this instantiation its fifth wave per SIMD: 96 -> 104 VGPRs)
         const int cpg = C / fin.G;
         const int ga = c / cpg, gb = (c + 3) / cpg;
         float ma, ra, mb2, rb2;
@@ -801,6 +803,8 @@ extern "C" int ofx_gn_apply_planes_oct(const float* x, int64_t ldx, int64_t n, i
       shift > 7 || !left_head || ((uintptr_t)left_head & 15) || !left_src || n_left < 1 || n_left > n_multi + 1 ||
       n_own + n_left != n_multi + 1)
     return OFX_EINVAL;
+  // the in-launch finalize needs >= 2 channels per group (its fallback for a third batch element in one block)
+  if (!mean && C / groups < 2) return OFX_EINVAL;
   if (n > 0) {
     const int RP = 256 / (C >> 2);
     const int64_t n_oct = ofx_cdiv(n + shift, 8);

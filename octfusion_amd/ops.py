@@ -1045,7 +1045,7 @@ class AuxGraph(NamedTuple):
     block_plan: tuple = None
 
 
-def _gn_launch(planes, aux_graph, elems):
+def _gn_launch(planes, aux_graph, elems, cpg=2):
     """(launch, finalize) of the apply step of a GroupNorm over `elems` elements.  launch: 'fp32' (ofx_gn_apply), or for a
     planes result 'oct' (ofx_gn_apply_planes_oct), 'block' (ofx_gn_apply_planes with the block plan) or 'plain'
     (ofx_gn_apply_planes without a plan); finalize: an ofx_gn_finalize launch precedes it -- otherwise mean / rstd are
@@ -1061,7 +1061,9 @@ def _gn_launch(planes, aux_graph, elems):
     octet launch has no fused variant above that bar, so an octet plan then takes the plain launch."""
     g = aux_graph if planes else None
     oct_plan, block_plan = (g.oct_plan, g.block_plan) if g is not None and AUX_PLAN else (None, None)
-    oct_fin = GN_OCT_FINALIZE and AUX_PLAN == 'oct' and oct_plan is not None and elems <= GN_OCT_FINALIZE_MAX_ELEMS
+    # (one channel per group -- cpg = 1 -- keeps the finalize launch: the octet launch's in-launch finalize needs >= 2, ofx.h)
+    oct_fin = (GN_OCT_FINALIZE and AUX_PLAN == 'oct' and oct_plan is not None and elems <= GN_OCT_FINALIZE_MAX_ELEMS
+               and cpg >= 2)
     finalize = GN_FINALIZE_LAUNCH or (g is not None and not GN_FUSE_AUX_FINALIZE and not oct_fin)
     if not planes:
         return 'fp32', finalize
@@ -1104,7 +1106,7 @@ def group_norm(x, batch_id, count, batch_size, weight, bias, groups, eps=1e-5, a
     w = weight.detach().reshape(-1)
     b = bias.detach().reshape(-1)
     mean = rstd = None
-    launch, finalize = _gn_launch(planes, aux_graph, n * C)
+    launch, finalize = _gn_launch(planes, aux_graph, n * C, C // groups)
     if finalize:
         mean = torch.empty(batch_size * C, dtype=torch.float32, device=dev)
         rstd = torch.empty(batch_size * C, dtype=torch.float32, device=dev)

@@ -47,28 +47,29 @@ def test_narrow_input_conv(cin, cout, d, nt, bias):
     ref = OM.graph_conv(x.double(), o_doc, d, sd['weights'].double(), sd['bias'].double() if bias else None, nt)
     assert ops.narrow_in_ok(cin, cout, nt if nt > 1 else 0)
     wide = torch.full((N, cout + 64), 7.0, device=dev())
-    ops.NARROW_IN_TAB_MIN_ROWS = 0                    # the table-driven launch at any size (product: from 512 k rows up)
-    with ops.stats_scope(dev()):
-        y = conv(x.to(dev()), doc, d, out=wide[:, 64:])
-        st = ops.get_stats(y)
-        assert y.data_ptr() == wide[:, 64:].data_ptr() and bool((wide[:, :64] == 7.0).all())
-        e = errors(y, ref)
-        assert e['rel_to_max'] < 2e-6, e
-        if N * cout >= (1 << 14):
-            assert st is not None
-            bid = doc.batch_id32(d).long()
-            want = torch.zeros(B, cout, 2, dtype=torch.float64, device=dev())
-            want[:, :, 0].index_add_(0, bid, y.double())
-            want[:, :, 1].index_add_(0, bid, y.double() ** 2)
-            assert float((st.view(B, cout, 2) - want).abs().max()) <= 1e-6 * float(want.abs().max())
-    # the CSR-walking launch of round 5 (one block per 64 rows) against the table-driven persistent one (the default)
-    ops.NARROW_IN_TAB = False
+    saved_min_rows = ops.NARROW_IN_TAB_MIN_ROWS
     try:
+        ops.NARROW_IN_TAB_MIN_ROWS = 0                # the table-driven launch at any size (product: from 512 k rows up)
+        with ops.stats_scope(dev()):
+            y = conv(x.to(dev()), doc, d, out=wide[:, 64:])
+            st = ops.get_stats(y)
+            assert y.data_ptr() == wide[:, 64:].data_ptr() and bool((wide[:, :64] == 7.0).all())
+            e = errors(y, ref)
+            assert e['rel_to_max'] < 2e-6, e
+            if N * cout >= (1 << 14):
+                assert st is not None
+                bid = doc.batch_id32(d).long()
+                want = torch.zeros(B, cout, 2, dtype=torch.float64, device=dev())
+                want[:, :, 0].index_add_(0, bid, y.double())
+                want[:, :, 1].index_add_(0, bid, y.double() ** 2)
+                assert float((st.view(B, cout, 2) - want).abs().max()) <= 1e-6 * float(want.abs().max())
+        # the CSR-walking launch of round 5 (one block per 64 rows) against the table-driven persistent one (the default)
+        ops.NARROW_IN_TAB = False
         with ops.stats_scope(dev()):
             y_csr = conv(x.to(dev()), doc, d)
     finally:
         ops.NARROW_IN_TAB = True
-        ops.NARROW_IN_TAB_MIN_ROWS = 1 << 19
+        ops.NARROW_IN_TAB_MIN_ROWS = saved_min_rows
     assert errors(y_csr, ref)['rel_to_max'] < 2e-6
     assert float((y_csr - y).abs().max()) <= 2e-6 * float(ref.abs().max())
     # A/B: the contraction path it replaces gives the same operator
