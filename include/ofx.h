@@ -781,6 +781,11 @@ int ofx_voxmesh_emit(int batch, int depth, int weld, void* ws, const int64_t* ve
  * uniform with the u + w > 1 reflection.  The random numbers are r_d = ofx_metrics_hash(seed, id, i, d) for point i
  * of the shape with id = ids[b] (int64 device array, NULL: b), d = 0 triangle, 1 and 2 barycentrics: the output
  * out [batch, n, 3] is a pure function of the inputs (bitwise, any launch geometry).  ws: ofx_surface_sample_ws_bytes.
+ * ofx_surface_sample_oriented: the same draw (same arguments, workspace and hash; `out` is bit-equal to
+ * ofx_surface_sample's) plus normals [batch, n, 3]: the unit normal (B - A) x (C - A) / |.| of the triangle drawn for
+ * each point, computed in fp64 from the un-normalised vertices (normalising scales and translates: same direction)
+ * and rounded once to fp32.  A zero-area triangle has probability 0 and is never drawn; a shape whose total area is 0
+ * is the caller's error (its normals are written as 0).  This is what the VAE encoder eats: Points(points, normals).
  * ofx_nn_matrix: d [na, nb] with d[i, j] = mean_p min_q |p - q|^2, p over a[i] ([na, n, 3]), q over b[j] ([nb, m, 3])
  * -- directed, so Chamfer is d_ab + d_ba^T (the reference's dl.mean + dr.mean); direct differences: a cloud against
  * itself gives exactly 0.  Any n, m >= 1.
@@ -791,6 +796,9 @@ int ofx_voxmesh_emit(int batch, int depth, int weld, void* ws, const int64_t* ve
 size_t ofx_surface_sample_ws_bytes(int batch, int64_t total_faces);
 int ofx_surface_sample(const float* verts, const int32_t* faces, const int64_t* offs, const int64_t* ids, int batch,
                        int64_t total_faces, int n, uint64_t seed, int normalize, void* ws, float* out, void* stream);
+int ofx_surface_sample_oriented(const float* verts, const int32_t* faces, const int64_t* offs, const int64_t* ids,
+                                int batch, int64_t total_faces, int n, uint64_t seed, int normalize, void* ws,
+                                float* out, float* normals, void* stream);
 int ofx_nn_matrix(const float* a, int64_t na, int n, const float* b, int64_t nb, int m, float* d, void* stream);
 int ofx_emd_matrix(const float* x, int64_t nx, const float* y, int64_t ny, int n, int m, float* e, void* stream);
 /* the sampler's counter hash (host): splitmix64 steps h <- mix(h + 0x9E3779B97F4A7C15 * (x + 1)) over x = id, i, d */

@@ -167,6 +167,7 @@ _SIGS = {
     'ofx_voxmesh_emit': (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p], True),
     'ofx_surface_sample_ws_bytes':(c_sz, [c_i, c_l], False),
     'ofx_surface_sample': (c_i, [c_p, c_p, c_p, c_p, c_i, c_l, c_i, c_u64, c_i, c_p, c_p, c_p], True),
+    'ofx_surface_sample_oriented': (c_i, [c_p, c_p, c_p, c_p, c_i, c_l, c_i, c_u64, c_i, c_p, c_p, c_p, c_p], True),
     'ofx_nn_matrix': (c_i, [c_p, c_l, c_i, c_p, c_l, c_i, c_p, c_p], True),
     'ofx_emd_matrix': (c_i, [c_p, c_l, c_p, c_l, c_i, c_i, c_p, c_p], True),
     'ofx_metrics_hash': (c_u64, [c_u64, c_l, c_l, c_i], False),

@@ -11,6 +11,8 @@
 //             first t with prefix[t] > (r_0 >> 11) * 2^-53 * total, barycentrics u = (r_1 >> 40) * 2^-24,
 //             w = (r_2 >> 40) * 2^-24, reflected to (1 - u, 1 - w) when (r_1 >> 40) + (r_2 >> 40) > 2^24;
 //             p = A + u (B - A) + w (C - A) on the normalised vertices.
+//             The oriented entry point adds the unit normal (B - A) x (C - A) / |.| of the drawn triangle, in fp64 from
+//             the raw vertices, rounded once (same kernel body: sp_sample_kernel<true>).
 //   NN        D[a, b] = mean_p min_q |p - q|^2, p over A[a], q over B[b], direct differences (a cloud against itself
 //             gives exactly 0).  Queries live in registers (8 per lane, packed in pairs: v_pk_* f32), targets stream
 //             through LDS as broadcast (x, y, z, .) reads, one block owns one query cloud and NN_BT target clouds.
@@ -144,10 +146,15 @@ __global__ __launch_bounds__(SP_T) void sp_prep_kernel(const float* __restrict__
   }
 }
 
+// ORIENTED: also write the unit normal (B - A) x (C - A) / |.| of the drawn triangle, from the raw vertices (the
+// normalisation is a positive scale and a translation: same direction, one rounding less).  The differences of fp32
+// coordinates are exact in fp64, so the normal is the fp32 rounding of the true one however thin the triangle is.
+// The draw itself -- hash, prefix search, barycentrics, point -- is this one body for both instantiations.
+template <bool ORIENTED>
 __global__ void sp_sample_kernel(const float* __restrict__ verts, const int32_t* __restrict__ faces,
                                  const int64_t* __restrict__ offs, const int64_t* __restrict__ ids, int batch, int n,
                                  uint64_t seed, const float* __restrict__ frame, const double* __restrict__ cdf,
-                                 float* __restrict__ out) {
+                                 float* __restrict__ out, float* __restrict__ normals) {
   const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= (int64_t)batch * n) return;
   const int b = (int)(g / n), i = (int)(g % n);
@@ -155,6 +162,7 @@ __global__ void sp_sample_kernel(const float* __restrict__ verts, const int32_t*
   float* o = out + g * 3;
   if (nf <= 0) {                                  // the caller refuses such shapes; never read an empty prefix
     o[0] = o[1] = o[2] = NAN;
+    if constexpr (ORIENTED) normals[g * 3 + 0] = normals[g * 3 + 1] = normals[g * 3 + 2] = NAN;
     return;
   }
   const double* c = cdf + foff;
@@ -176,17 +184,31 @@ __global__ void sp_sample_kernel(const float* __restrict__ verts, const int32_t*
   const float* fr = frame + (int64_t)b * 4;
   const int32_t* tri = faces + (foff + lo) * 3;
   const float* v = verts + voff * 3;
-  float p[3][3];
+  float raw[3][3], p[3][3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     const float* q = v + (int64_t)tri[k] * 3;
 #pragma unroll
-    for (int a = 0; a < 3; ++a) p[k][a] = __fmul_rn(__fsub_rn(q[a], fr[a]), fr[3]);
+    for (int a = 0; a < 3; ++a) {
+      raw[k][a] = q[a];
+      p[k][a] = __fmul_rn(__fsub_rn(raw[k][a], fr[a]), fr[3]);
+    }
   }
 #pragma unroll
   for (int a = 0; a < 3; ++a)
     o[a] = __fadd_rn(__fadd_rn(p[0][a], __fmul_rn(u, __fsub_rn(p[1][a], p[0][a]))),
                      __fmul_rn(w, __fsub_rn(p[2][a], p[0][a])));
+  if constexpr (ORIENTED) {
+    const double ax = (double)raw[1][0] - raw[0][0], ay = (double)raw[1][1] - raw[0][1], az = (double)raw[1][2] - raw[0][2];
+    const double bx = (double)raw[2][0] - raw[0][0], by = (double)raw[2][1] - raw[0][1], bz = (double)raw[2][2] - raw[0][2];
+    const double cx = ay * bz - az * by, cy = az * bx - ax * bz, cz = ax * by - ay * bx;
+    const double len = sqrt(cx * cx + cy * cy + cz * cz);
+    const double inv = len > 0.0 ? 1.0 / len : 0.0;      // only a shape of total area 0 can draw such a triangle
+    float* nm = normals + g * 3;
+    nm[0] = (float)(cx * inv);
+    nm[1] = (float)(cy * inv);
+    nm[2] = (float)(cz * inv);
+  }
 }
 
 struct SpWs {
@@ -460,9 +482,10 @@ extern "C" size_t ofx_surface_sample_ws_bytes(int batch, int64_t total_faces) {
   return sp_layout(batch, total_faces, nullptr, nullptr);
 }
 
-extern "C" int ofx_surface_sample(const float* verts, const int32_t* faces, const int64_t* offs, const int64_t* ids,
-                                  int batch, int64_t total_faces, int n, uint64_t seed, int normalize, void* ws,
-                                  float* out, void* stream) {
+namespace {
+
+int sp_run(const float* verts, const int32_t* faces, const int64_t* offs, const int64_t* ids, int batch,
+           int64_t total_faces, int n, uint64_t seed, int normalize, void* ws, float* out, float* normals, void* stream) {
   if (!verts || !faces || !offs || !ws || !out || batch < 1 || n < 1 || total_faces < 1 ||
       ofx_cdiv((int64_t)batch * n, 256) > INT32_MAX)
     return OFX_EINVAL;
@@ -471,11 +494,28 @@ extern "C" int ofx_surface_sample(const float* verts, const int32_t* faces, cons
   sp_layout(batch, total_faces, (char*)ws, &w);
   sp_prep_kernel<<<batch, SP_T, 0, st>>>(verts, faces, offs, batch, normalize ? 1 : 0, w.frame, w.cdf);
   OFX_LAUNCH_CHECK();
-  const int64_t total = (int64_t)batch * n;
-  sp_sample_kernel<<<(unsigned)ofx_cdiv(total, 256), 256, 0, st>>>(verts, faces, offs, ids, batch, n, seed, w.frame,
-                                                                   w.cdf, out);
+  const unsigned grid = (unsigned)ofx_cdiv((int64_t)batch * n, 256);
+  if (normals)
+    sp_sample_kernel<true><<<grid, 256, 0, st>>>(verts, faces, offs, ids, batch, n, seed, w.frame, w.cdf, out, normals);
+  else
+    sp_sample_kernel<false><<<grid, 256, 0, st>>>(verts, faces, offs, ids, batch, n, seed, w.frame, w.cdf, out, nullptr);
   OFX_LAUNCH_CHECK();
   return OFX_OK;
+}
+
+}  // namespace
+
+extern "C" int ofx_surface_sample(const float* verts, const int32_t* faces, const int64_t* offs, const int64_t* ids,
+                                  int batch, int64_t total_faces, int n, uint64_t seed, int normalize, void* ws,
+                                  float* out, void* stream) {
+  return sp_run(verts, faces, offs, ids, batch, total_faces, n, seed, normalize, ws, out, nullptr, stream);
+}
+
+extern "C" int ofx_surface_sample_oriented(const float* verts, const int32_t* faces, const int64_t* offs,
+                                           const int64_t* ids, int batch, int64_t total_faces, int n, uint64_t seed,
+                                           int normalize, void* ws, float* out, float* normals, void* stream) {
+  if (!normals) return OFX_EINVAL;
+  return sp_run(verts, faces, offs, ids, batch, total_faces, n, seed, normalize, ws, out, normals, stream);
 }
 
 extern "C" int ofx_nn_matrix(const float* a, int64_t na, int n, const float* b, int64_t nb, int m, float* d,

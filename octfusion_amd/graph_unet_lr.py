@@ -272,6 +272,16 @@ class ResnetBlock(nn.Module):
 class QKVAttention(nn.Module):
     """reference modules.py:538-547 -- computed by ofx_attention."""
 
+    @torch.no_grad()
+    def forward(self, qkv):
+        """The reference's ``forward(qkv)``: qkv [N, 3 * ch, T] (N = batch * heads, channels q | k | v) -> [N, ch, T].
+        AttentionBlock calls ops.attention on its row layout directly; this is the same launch with one head per
+        element of N (the two transposes are layout plumbing for callers that hold the reference's tensor)."""
+        N, c3, T = qkv.shape
+        ch = c3 // 3
+        rows = qkv.float().permute(0, 2, 1).reshape(N * T, c3)
+        return ops.attention(rows, N, T, 1).view(N, T, ch).permute(0, 2, 1).contiguous().to(qkv.dtype)
+
 
 class AttentionBlock(nn.Module):
     """reference modules.py:515-535."""

@@ -5,8 +5,8 @@ Mirror of reference models/networks/dualoctree_networks/graph_vae.py (ctor :52-1
 octree_decoder :171-223, create_child_octree :236-244, decode_code :300-324) and the VAE
 flavoured GraphDownsample / GraphUpsample (dualoctree_networks/modules.py:39-95).  The full
 module tree (encoder included) is constructed so a reference VAE checkpoint loads with
-strict=True; only the decoder has a forward here (the encoder runs at training time only,
-SURVEY.md section 8: out of scope).  NeuralMPU SDF evaluation is the next row (section 8f).
+strict=True.  forward / extract_code (:246-298) are the auto-encoder's entry points: shape in, reconstruction out
+(reconstruct.py drives them); training goes through vae_training.
 """
 import torch
 import torch.nn as nn
@@ -132,8 +132,15 @@ class GraphVAE(nn.Module):
     def encode(self, data, doctree, noise=None, sample=True):
         """graph_vae.py:162-170 / 291-298: KL_conv -> DiagonalGaussianDistribution (distributions.py:24-37).
         Returns (code [N, embed_dim], mean, logvar); code = mean + exp(logvar / 2) * noise, or the mean."""
-        h = self.octree_encoder_step(data, doctree)[self.depth_stop]
-        mean, logvar = torch.chunk(self.KL_conv(h), 2, dim=1)
+        return self._sample(self._posterior(data, doctree), noise, sample)
+
+    def _posterior(self, data, doctree):
+        """[N, 2 * embed_dim] parameters of the posterior (octree_encoder, graph_vae.py:162-169)."""
+        return self.KL_conv(self.octree_encoder_step(data, doctree)[self.depth_stop])
+
+    @staticmethod
+    def _sample(params, noise=None, sample=True):
+        mean, logvar = torch.chunk(params, 2, dim=1)
         logvar = torch.clamp(logvar, -30.0, 20.0)
         if not sample:
             return mean.contiguous(), mean, logvar
@@ -186,4 +193,52 @@ class GraphVAE(nn.Module):
             output['mpus'] = self.neural_mpu(pos, out[1], out[2])
         # graph_vae.py:319-323: the SDF field of the decoded shape (callable on pts [n,4]; calc_sdf sweeps it)
         output['neural_mpu'] = mpu.MpuField(self.full_depth, self.depth_out, out[1][self.depth_out], out[2])
+        return output
+
+    @staticmethod
+    def _input_feature(doctree_in, data):
+        """graph_vae.py:131-132: the 'ND' feature of the input octree, unless the caller brings its own rows."""
+        return doctree_in.get_input_feature() if data is None else data
+
+    @torch.no_grad()
+    def extract_code(self, octree_in, noise=None, data=None):
+        """graph_vae.py:291-298: (posterior sample [N_depth_stop, embed_dim], DualOctree(octree_in)).  noise: the
+        normal draws to use (default: one randn_like from torch's generator, as posterior.sample() makes one draw);
+        data [N_depth, channel_in]: input feature replacing the octree's own (an octree that was not built from points
+        has none)."""
+        doctree_in = DualOctree(octree_in)
+        code, _, _ = self.encode(self._input_feature(doctree_in, data), doctree_in, noise=noise)
+        return code, doctree_in
+
+    @torch.no_grad()
+    def forward(self, octree_in, octree_out=None, pos=None, evaluate=False, noise=None, data=None, mpu_depth=None):
+        """graph_vae.py:246-289: encode octree_in, decode on octree_out -- or, without one, on the child octree of
+        octree_in, grown by the predicted splits.  Returns the reference's dict: logits, reg_voxs, octree_out, kl_loss
+        (mean of the posterior's kl()), code_max, code_min, neural_mpu and, with pos [n, 4], mpus.
+
+        noise: the posterior's normal draws.  None draws them from torch's generator exactly as the reference does:
+        once, and once more under evaluate (graph_vae.py:266-270) -- the second draw is the code.  neural_mpu evaluates
+        the SDF at depth_stop, the depth the reference's forward wrapper reads (graph_vae.py:284-287; decode_code's
+        reads depth_out); mpu_depth selects another depth in [depth_stop, depth_out].  data: as extract_code."""
+        from .vae_training import kl_sample
+        doctree_in = DualOctree(octree_in)
+        update_octree = octree_out is None
+        if update_octree:
+            octree_out = self.create_child_octree(octree_in)
+        doctree_out = doctree_in if octree_out is octree_in else DualOctree(octree_out)
+        params = self._posterior(self._input_feature(doctree_in, data), doctree_in)
+        code = self._sample(params, noise)[0]
+        if evaluate and noise is None:
+            code = self._sample(params)[0]
+        logits, reg_voxs, octree_out = self.octree_decoder(code, doctree_out, update_octree=update_octree)
+        # kl_sample also samples; only its KL mean is used here (the code above is encode()'s, bit for bit)
+        output = {'logits': logits, 'reg_voxs': reg_voxs, 'octree_out': octree_out,
+                  'kl_loss': kl_sample(params, None, params.shape[1] // 2)[1],
+                  'code_max': code.max(), 'code_min': code.min()}
+        if pos is not None:
+            output['mpus'] = self.neural_mpu(pos, reg_voxs, octree_out)
+        d = self.depth_stop if mpu_depth is None else int(mpu_depth)
+        if not self.depth_stop <= d <= self.depth_out:
+            raise ValueError('mpu_depth %d outside [%d, %d]' % (d, self.depth_stop, self.depth_out))
+        output['neural_mpu'] = mpu.MpuField(self.full_depth, d, reg_voxs[d], octree_out)
         return output

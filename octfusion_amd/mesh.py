@@ -1,4 +1,5 @@
-"""Mesh export of the generate path: marching cubes on the device (csrc/ofx_mesh.hip) and an OBJ writer.
+"""Mesh export of the generate path: marching cubes on the device (csrc/ofx_mesh.hip), an OBJ writer and a PLY
+point-cloud writer.
 
 Replaces the reference's host tail (export_mesh, models/octfusion_model_union.py:435-468; create_mesh,
 utils/util_dualoctree.py:120-142): skimage.measure.marching_cubes(sdf, level=0) per shape, vertices mapped by
@@ -321,3 +322,61 @@ def read_obj(path):
     v = np.asarray(vs, np.float64).astype(np.float32).reshape(-1, 3)
     f = (np.asarray(fs, np.int64) - 1).astype(np.int32).reshape(-1, 3)
     return v, f
+
+
+_PLY_XYZ = [('x', '<f4'), ('y', '<f4'), ('z', '<f4')]
+_PLY_NRM = [('nx', '<f4'), ('ny', '<f4'), ('nz', '<f4')]
+
+
+def write_ply(path, points, normals=None):
+    """Write a point cloud as binary little-endian PLY: one ``vertex`` element with float32 properties ``x y z`` and,
+    with normals, ``nx ny nz`` (the layout of the reference's points2ply, utils/util_dualoctree.py:171-197, and of the
+    ``input.ply`` its inference writes).  Vectorised: one array, one write; zero points give a valid header-only
+    file."""
+    p = points.detach().cpu().numpy() if torch.is_tensor(points) else np.asarray(points)
+    p = np.ascontiguousarray(p, np.float32).reshape(-1, 3)
+    cols, props = [p], list(_PLY_XYZ)
+    if normals is not None:
+        q = normals.detach().cpu().numpy() if torch.is_tensor(normals) else np.asarray(normals)
+        q = np.ascontiguousarray(q, np.float32).reshape(-1, 3)
+        if len(q) != len(p):
+            raise ValueError('write_ply: %d normals for %d points' % (len(q), len(p)))
+        cols.append(q)
+        props += _PLY_NRM
+    head = 'ply\nformat binary_little_endian 1.0\nelement vertex %d\n' % len(p)
+    head += ''.join('property float %s\n' % name for name, _ in props) + 'end_header\n'
+    d = os.path.dirname(path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    with open(path, 'wb') as fh:
+        fh.write(head.encode('ascii'))
+        fh.write(np.concatenate(cols, axis=1).astype('<f4').tobytes())
+
+
+def read_ply(path):
+    """(points [n, 3] float32, normals [n, 3] float32 or None) of a PLY as ``write_ply`` writes it: binary
+    little-endian, one vertex element whose properties are all float32 and begin with x y z [nx ny nz]."""
+    with open(path, 'rb') as fh:
+        raw = fh.read()
+    end = raw.find(b'end_header\n')
+    if not raw.startswith(b'ply\n') or end < 0:
+        raise ValueError('read_ply: %s is not a PLY file' % path)
+    lines = raw[:end].decode('ascii').split('\n')
+    if 'format binary_little_endian 1.0' not in lines:
+        raise ValueError('read_ply: %s is not binary little-endian' % path)
+    n, props = None, []
+    for ln in lines:
+        t = ln.split()
+        if t[:2] == ['element', 'vertex']:
+            n = int(t[2])
+        elif t[:1] == ['element']:
+            raise ValueError('read_ply: %s has elements other than vertex' % path)
+        elif t[:1] == ['property']:
+            if t[1] not in ('float', 'float32'):
+                raise ValueError('read_ply: property %s of %s is not float32' % (t[-1], path))
+            props.append(t[2])
+    if n is None or props[:3] != ['x', 'y', 'z']:
+        raise ValueError('read_ply: %s has no x y z vertex properties' % path)
+    body = np.frombuffer(raw, '<f4', count=n * len(props), offset=end + len(b'end_header\n')).reshape(n, len(props))
+    nrm = body[:, 3:6].copy() if props[3:6] == ['nx', 'ny', 'nz'] else None
+    return body[:, :3].copy(), nrm

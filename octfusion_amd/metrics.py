@@ -36,13 +36,15 @@ def _clouds(X, what):
     return X.to(device=dev, dtype=torch.float32).contiguous()
 
 
-def sample_surface(meshes, n=2048, seed=0, normalize=True, ids=None):
+def sample_surface(meshes, n=2048, seed=0, normalize=True, ids=None, normals=False):
     """[B, n, 3] float32 device tensor of points drawn uniformly by area from each mesh of ``meshes``: the list that
     ``mesh.marching_cubes`` returns, or ``(verts, faces)`` pairs as ``mesh.read_obj`` reads them (numpy or tensors,
     faces 0-based).  normalize: first map each mesh to (v - bbox centre) * 2 / max bbox extent, as the reference's
     scale_to_unit_cube (padding 0) does before trimesh's mesh.sample.  ids: one int per mesh keying its random
-    numbers (default: the position in the list), so a shape gets the same points in any batch.  Raises ValueError
-    naming the shape for a mesh without faces or with an out-of-range index."""
+    numbers (default: the position in the list), so a shape gets the same points in any batch.  normals: return
+    ``(points, normals)``, normals [B, n, 3] = the unit face normal (B - A) x (C - A) / |.| of the triangle each point
+    was drawn from (ofx_surface_sample_oriented; the points are the same bits) -- the oriented cloud the VAE encoder
+    takes.  Raises ValueError naming the shape for a mesh without faces or with an out-of-range index."""
     _lib.require_device()
     if int(n) < 1:
         raise ValueError('sample_surface: n must be >= 1')
@@ -76,9 +78,14 @@ def sample_surface(meshes, n=2048, seed=0, normalize=True, ids=None):
     T = int(sum(nf))
     ws = torch.empty(_lib.lib().ofx_surface_sample_ws_bytes(B, T), dtype=torch.uint8, device=dev)
     out = torch.empty(B, int(n), 3, dtype=torch.float32, device=dev)
-    _lib.call('ofx_surface_sample', _lib.ptr(V), _lib.ptr(F), _lib.ptr(offs), _lib.ptr(idt), B, T, int(n),
-              int(seed) & (2 ** 64 - 1), 1 if normalize else 0, _lib.ptr(ws), _lib.ptr(out), _lib.stream())
-    return out
+    args = (_lib.ptr(V), _lib.ptr(F), _lib.ptr(offs), _lib.ptr(idt), B, T, int(n), int(seed) & (2 ** 64 - 1),
+            1 if normalize else 0, _lib.ptr(ws), _lib.ptr(out))
+    if not normals:
+        _lib.call('ofx_surface_sample', *args, _lib.stream())
+        return out
+    nrm = torch.empty_like(out)
+    _lib.call('ofx_surface_sample_oriented', *args, _lib.ptr(nrm), _lib.stream())
+    return out, nrm
 
 
 def nn_matrix(A, B):

@@ -1,0 +1,285 @@
+"""Reconstruction driver: an existing shape in, the GraphVAE's reconstruction of it out, with a Chamfer score.
+
+Mirror of the reference's ``OctFusionVAEModel.inference`` (models/octfusion_model_vae.py:189-205: autoencoder.forward(
+octree_in, evaluate=True) -> get_sdfs -> export_mesh -> input.ply) and of ``calc_chamfer``
+(utils/util_dualoctree.py:152-168), on the device from the point cloud to the mesh:
+
+    oriented points -> Points.clip -> build_octree_batch -> GraphVAE.forward(evaluate=True) -> mpu.calc_sdf ->
+    mesh.marching_cubes -> <out>/<name>/0.obj, <out>/<name>/input.ply, <out>/metrics.json
+
+* Inputs are directories holding the reference's ``pointcloud.npz`` (keys ``points``, ``normals``;
+  datasets/dualoctree_snet.py:36-47: points / point_scale, then clip to the open cube), or, with ``--from-mesh``, OBJ
+  files -- also the ones ``generate.py --mesh`` writes -- sampled with their face normals on the device
+  (metrics.sample_surface(normals=True)) after the max-extent normalisation to [-1, 1] and a factor ``--fit``.
+* The SDF is read at the decoder's finest depth (``--mpu-depth``, default depth_out) -- see DESIGN.md 4.9: the
+  reference's inference reads depth_stop through forward's wrapper, which ``--mpu-depth <depth_stop>`` reproduces.
+* The score is calc_chamfer's pair: n surface samples of each side, not normalised, the two directed mean squared
+  nearest-neighbour distances x 1e5.  The samples are the project's (counter hash), not trimesh's with seed 101.
+* A shape whose reconstruction is empty gets no OBJ and ``null`` scores, with a warning; the rest go on.
+
+    python -m octfusion_amd.reconstruct --config snet_uncond --vae vae.pth --input data/02691156/1a04e3 --out recon
+    python -m octfusion_amd.reconstruct --config snet_uncond --vae vae.pth --from-mesh --input samples/0.obj --out recon
+"""
+import argparse
+import json
+import os
+import time
+import warnings
+
+import numpy as np
+import torch
+
+from . import configs, mesh, metrics, mpu
+from .octree import Points, build_octree_batch
+
+CHAMFER_SCALE = 1.0e5           # utils/util_dualoctree.py:153
+# --points / --chamfer-points default: a choice (the reference has no call site of calc_chamfer and ships its clouds
+# ready-made); about one point per depth-8 surface cell
+POINTS = 100000
+
+
+def recon_config(name):
+    """What the driver needs of a config name of octfusion_amd.configs: the VAE's octree depths and point_scale."""
+    kw = configs.vae_params(name)
+    return {'name': name, 'depth': kw['depth'], 'full_depth': kw['full_depth'], 'point_scale': mesh.mesh_scale(name)}
+
+
+def shape_name(path):
+    """The output folder of an input, as inference derives it (octfusion_model_vae.py:193-197): the base name up to its
+    last '.'; for a ``pointcloud.npz`` file, its directory's."""
+    path = os.path.normpath(path)
+    if os.path.basename(path) == 'pointcloud.npz':
+        path = os.path.dirname(path)
+    name = os.path.basename(path)
+    pos = name.rfind('.')
+    if pos != -1:
+        name = name[:pos]
+    if not name:
+        raise ValueError('reconstruct: %s leaves no name once its suffix is removed' % path)
+    return name
+
+
+def read_inputs(paths, from_mesh=False):
+    """[{name, kind, path, points + normals | verts + faces}] (numpy, file units) of the input paths; kind 'points' for
+    a directory with pointcloud.npz (or the file itself), 'mesh' for an OBJ with from_mesh."""
+    out, seen = [], set()
+    for p in paths:
+        name = shape_name(p)
+        if name in seen:
+            raise ValueError('reconstruct: two inputs are named %r' % name)
+        seen.add(name)
+        if from_mesh:
+            if not p.lower().endswith('.obj'):
+                raise ValueError('reconstruct: --from-mesh takes .obj files, got %s' % p)
+            v, f = mesh.read_obj(p)
+            if len(f) == 0:
+                raise ValueError('reconstruct: %s has no faces' % p)
+            out.append({'name': name, 'kind': 'mesh', 'path': p, 'verts': v, 'faces': f})
+        else:
+            f = p if os.path.basename(p) == 'pointcloud.npz' else os.path.join(p, 'pointcloud.npz')
+            with np.load(f) as z:
+                pts, nrm = np.asarray(z['points'], np.float32), np.asarray(z['normals'], np.float32)
+            if pts.ndim != 2 or pts.shape[1] != 3 or nrm.shape != pts.shape:
+                raise ValueError('reconstruct: %s: points %s, normals %s' % (f, pts.shape, nrm.shape))
+            out.append({'name': name, 'kind': 'points', 'path': p, 'points': pts, 'normals': nrm})
+    return out
+
+
+def _cloud(side, n, seed):
+    """[1, m, 3]: n surface samples of a (verts, faces) mesh in its own frame, or a given [m, 3] cloud."""
+    if torch.is_tensor(side):
+        return side.reshape(1, -1, 3)
+    return metrics.sample_surface([side], n=n, seed=seed, normalize=False)
+
+
+def chamfer(mesh_a, mesh_b, n, seed=0):
+    """calc_chamfer(gt, pred, point_num) (utils/util_dualoctree.py:152-168): (chamfer_a, chamfer_b) = the mean squared
+    distance from the samples of b to their nearest sample of a, and from those of a to b, x 1e5.  Each side is a
+    ``(verts, faces)`` mesh, of which n surface points are drawn without normalising, or an [m, 3] cloud taken as it
+    is.  Both sides draw with the same seed and shape id, so a mesh against itself scores exactly (0, 0) -- and the
+    two sample sets share their triangle and barycentric random numbers, so for two similar meshes the samples are
+    correlated and the score lies slightly below what independent draws (the reference's) give.  Two launches of
+    nn_matrix with one cloud on each side; at one pair nn_matrix runs on a single block, over n^2 point pairs per
+    direction.  One host read."""
+    A, B = _cloud(mesh_a, n, seed), _cloud(mesh_b, n, seed)
+    d = torch.cat([metrics.nn_matrix(B, A).reshape(1), metrics.nn_matrix(A, B).reshape(1)]).double() * CHAMFER_SCALE
+    ca, cb = d.tolist()
+    return ca, cb
+
+
+def _frame(verts):
+    """(centre [3], scale) of the sampler's normalisation: (v - centre) * scale fills the [-1, 1] max-extent cube."""
+    lo, hi = verts.min(0).values, verts.max(0).values
+    ext = float((hi - lo).max())
+    return (lo + hi) * 0.5, (2.0 / ext if ext > 0 else 1.0)
+
+
+def _lap(timings, name, t0, device):
+    if timings is None:
+        return t0
+    if device.type == 'cuda':
+        torch.cuda.synchronize(device)
+    t1 = time.perf_counter()
+    timings[name] = timings.get(name, 0.0) + t1 - t0
+    return t1
+
+
+@torch.no_grad()
+def reconstruct(vae, cfg, inputs, device, sdf_resolution=256, sdf_scale=0.9, level=0.0, clean=False, batch=8, seed=0,
+                points=POINTS, chamfer_points=POINTS, fit=None, mpu_depth=None, out_dir=None, timings=None):
+    """Reconstruct every shape of ``inputs`` (read_inputs) through ``vae``, ``batch`` shapes per call.  cfg:
+    recon_config(name), or a dict with depth, full_depth, point_scale.  points: samples per mesh input; fit: factor
+    on the normalised mesh samples (default sdf_scale); mpu_depth: depth the SDF is read at (default depth_out);
+    chamfer_points: samples per side of the score (0: no score).  The posterior noise comes from torch's generator,
+    seeded with ``seed`` once at the start.  Writes <out_dir>/<name>/0.obj, <name>/input.ply and metrics.json when
+    out_dir is given.  Returns the metrics dict; ``result['meshes'][name]`` holds the device meshes."""
+    device = torch.device(device)
+    ps = float(cfg['point_scale'])
+    fit = float(sdf_scale if fit is None else fit)
+    d_mpu = vae.depth_out if mpu_depth is None else int(mpu_depth)
+    torch.manual_seed(seed)
+    shapes, meshes = {}, {}
+    for g0 in range(0, len(inputs), batch):
+        group = inputs[g0:g0 + batch]
+        t0 = time.perf_counter()
+        # ---- oriented clouds in the encoder's frame, [-1, 1]^3
+        clouds, gts = [None] * len(group), [None] * len(group)
+        mesh_pos = [k for k, it in enumerate(group) if it['kind'] == 'mesh']
+        if mesh_pos:
+            vf = [(torch.from_numpy(group[k]['verts']).to(device), torch.from_numpy(group[k]['faces']).to(device))
+                  for k in mesh_pos]
+            p, n = metrics.sample_surface(vf, n=points, seed=seed, normalize=True, ids=[g0 + k for k in mesh_pos],
+                                          normals=True)
+            for j, k in enumerate(mesh_pos):
+                clouds[k] = Points(p[j] * fit, n[j])
+                c, s = _frame(vf[j][0])
+                gts[k] = ((vf[j][0] - c) * (s * fit * ps), vf[j][1])        # the input mesh in the output frame
+        for k, it in enumerate(group):
+            if it['kind'] == 'points':
+                clouds[k] = Points(torch.from_numpy(it['points']).to(device) / ps,
+                                   torch.from_numpy(it['normals']).to(device))
+        for k, c in enumerate(clouds):
+            c.clip(-1.0, 1.0)
+            if c.points.shape[0] == 0:
+                raise ValueError('reconstruct: %s has no point inside the cube' % group[k]['path'])
+        t0 = _lap(timings, 'sample', t0, device)
+        # ---- encode, decode (growing the octree), SDF lattice, mesh
+        octree_in = build_octree_batch(clouds, cfg['depth'], cfg['full_depth'])
+        t0 = _lap(timings, 'octree', t0, device)
+        out = vae.forward(octree_in, evaluate=True, mpu_depth=d_mpu)
+        t0 = _lap(timings, 'vae_forward', t0, device)
+        sdfs = mpu.calc_sdf(out['neural_mpu'], len(group), size=sdf_resolution, bbmin=-sdf_scale, bbmax=sdf_scale)
+        t0 = _lap(timings, 'sdf', t0, device)
+        recon = mesh.marching_cubes(sdfs, level=level, bbmin=-sdf_scale, bbmax=sdf_scale, scale=ps, clean=clean)
+        t0 = _lap(timings, 'mesh', t0, device)
+        # ---- score and files
+        for k, it in enumerate(group):
+            name, (v, f) = it['name'], recon[k]
+            rec = {'gt': it['kind'], 'input_points': int(clouds[k].points.shape[0]), 'vertices': int(v.shape[0]),
+                   'faces': int(f.shape[0]), 'chamfer_a': None, 'chamfer_b': None, 'obj': None}
+            if f.shape[0] == 0:
+                warnings.warn('reconstruct: %s: marching cubes found no surface, no mesh written' % name)
+            elif chamfer_points:
+                gt = gts[k]
+                if gt is None:                    # point-cloud input: the points the encoder saw, in file units
+                    pts = clouds[k].points
+                    if pts.shape[0] > chamfer_points:
+                        pts = pts[torch.arange(chamfer_points, device=device) * pts.shape[0] // chamfer_points]
+                    gt = pts * ps
+                rec['chamfer_a'], rec['chamfer_b'] = chamfer(gt, (v, f), chamfer_points, seed)
+            shapes[name] = rec
+            meshes[name] = (v, f)
+        t0 = _lap(timings, 'chamfer', t0, device)
+        if out_dir is not None:
+            for k, it in enumerate(group):
+                d = os.path.join(out_dir, it['name'])
+                os.makedirs(d, exist_ok=True)
+                if shapes[it['name']]['faces']:
+                    mesh.write_obj(os.path.join(d, '0.obj'), *recon[k])
+                    shapes[it['name']]['obj'] = os.path.join(it['name'], '0.obj')
+                mesh.write_ply(os.path.join(d, 'input.ply'), clouds[k].points, clouds[k].normals)
+            t0 = _lap(timings, 'write', t0, device)
+    res = {'config': cfg.get('name'), 'point_scale': ps, 'sdf_resolution': sdf_resolution, 'sdf_scale': sdf_scale,
+           'mpu_depth': d_mpu, 'fit': fit, 'seed': seed, 'chamfer_points': chamfer_points,
+           'chamfer_scale': CHAMFER_SCALE, 'shapes': shapes}
+    if timings is not None:
+        res['phase_seconds'] = dict(timings)
+    if out_dir is not None:
+        os.makedirs(out_dir, exist_ok=True)
+        with open(os.path.join(out_dir, 'metrics.json'), 'w') as fh:
+            json.dump(res, fh, indent=1)
+    res['meshes'] = meshes
+    return res
+
+
+def parser():
+    ap = argparse.ArgumentParser(prog='python -m octfusion_amd.reconstruct', description=__doc__.split('\n\n')[0])
+    ap.add_argument('--config', default='snet_uncond', choices=sorted(configs.CONFIGS))
+    ap.add_argument('--vae', default=None, help='GraphVAE checkpoint (seeded random weights when absent)')
+    ap.add_argument('--allow-pickle', action='store_true',
+                    help='read the checkpoint file with the full unpickler (only for files you trust)')
+    ap.add_argument('--input', nargs='+', required=True, metavar='PATH',
+                    help='directories holding pointcloud.npz (keys points, normals); with --from-mesh, .obj files')
+    ap.add_argument('--out', required=True, metavar='DIR',
+                    help='writes DIR/<name>/0.obj, DIR/<name>/input.ply and DIR/metrics.json')
+    ap.add_argument('--from-mesh', action='store_true',
+                    help='inputs are OBJ meshes: sampled with face normals on the device after mapping each to the '
+                         '[-1, 1] max-extent cube')
+    ap.add_argument('--points', type=int, default=POINTS, help='with --from-mesh: surface samples per mesh')
+    ap.add_argument('--fit', type=float, default=None,
+                    help='with --from-mesh: factor on the normalised samples.  Default: sdf_scale (0.9), the box the '
+                         'meshes are extracted in -- a choice of this driver, not a value of the reference, which '
+                         'only reads ready-made clouds')
+    ap.add_argument('--sdf-resolution', type=int, default=256)
+    ap.add_argument('--clean', action='store_true', help='keep only the largest connected component of every mesh')
+    ap.add_argument('--batch', type=int, default=8, help='shapes per call')
+    ap.add_argument('--seed', type=int, default=0, help='seeds the surface sampler and the posterior noise')
+    ap.add_argument('--mpu-depth', type=int, default=None,
+                    help='octree depth the SDF is read at (default: depth_out, what decode_code reads; the '
+                         'reference\'s inference reads depth_stop)')
+    ap.add_argument('--chamfer-points', type=int, default=POINTS,
+                    help='surface samples per side of the Chamfer score (default: the --points default, a choice: '
+                         'the reference never calls calc_chamfer); 0: no score.  The score of one shape is two '
+                         'launches over N^2 point pairs, each on a single block of the device (DESIGN.md 4.9): '
+                         'the default is slow, 2048 is cheap')
+    return ap
+
+
+def parse_args(argv=None):
+    args = parser().parse_args(argv)
+    if args.points < 1 or args.batch < 1 or args.chamfer_points < 0 or args.sdf_resolution < 2:
+        raise ValueError('--points, --batch >= 1, --chamfer-points >= 0 and --sdf-resolution >= 2 are required')
+    return args
+
+
+def build_vae(config, vae_ckpt=None, allow_pickle=False):
+    """The config's GraphVAE on the CPU: the checkpoint's weights, or seeded random ones (as generate.py)."""
+    from . import checkpoint, synthetic
+    from .graph_vae import GraphVAE
+    vae = GraphVAE(**configs.vae_params(config))
+    if vae_ckpt:
+        checkpoint.load_vae(vae_ckpt, vae, allow_pickle=allow_pickle)
+    else:
+        vae.load_state_dict(synthetic.random_state_dict(vae))
+    return vae
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    inputs = read_inputs(args.input, args.from_mesh)
+    from . import _lib
+    _lib.require_device()
+    device = torch.device('cuda', torch.cuda.current_device())
+    vae = build_vae(args.config, args.vae, args.allow_pickle).to(device).eval()
+    timings = {}
+    res = reconstruct(vae, recon_config(args.config), inputs, device, sdf_resolution=args.sdf_resolution,
+                      clean=args.clean, batch=args.batch, seed=args.seed, points=args.points,
+                      chamfer_points=args.chamfer_points, fit=args.fit, mpu_depth=args.mpu_depth, out_dir=args.out,
+                      timings=timings)
+    res.pop('meshes')
+    print(json.dumps(res))
+    return res
+
+
+if __name__ == '__main__':
+    main()
