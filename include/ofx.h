@@ -804,6 +804,35 @@ int ofx_emd_matrix(const float* x, int64_t nx, const float* y, int64_t ny, int n
 /* the sampler's counter hash (host): splitmix64 steps h <- mix(h + 0x9E3779B97F4A7C15 * (x + 1)) over x = id, i, d */
 uint64_t ofx_metrics_hash(uint64_t seed, int64_t shape, int64_t point, int draw);
 
+/* ------------------------------------------------------------------ SDF training samples (csrc/ofx_sdfdata.hip)
+ * The reference's tools/repair_mesh.py sample_sdf (:293-334) and sample_occu (:358-375) on an SDF lattice
+ * sdf [S, S, S] fp32, x slowest (the reference's sdf[x, y, z]); tests/sdfdata_oracle.py restates both with numpy.
+ * fp16 outputs are uint16 bit patterns, rounded to nearest even once (numpy.astype).
+ * ofx_sdf_sample_nodes: xyz [n_nodes, 3] int32 = the node coordinates of n_depths consecutive octree depths starting
+ *   at depth_start, concatenated depth-major in node order; depth_off [n_depths + 1] (int64 device) = where each depth
+ *   begins.  Candidate g = i*k + j, sample j of node i at depth d: p = fl32(fl32(node + u) * fl32(S * 2^-d)) with
+ *   u = u[g, 0..2] (fp32 [n_nodes*k, 3]) or, u == NULL, u_c = (ofx_metrics_hash(seed, shape, g, c) >> 40) * 2^-24.
+ *   Kept iff 0 <= p < S - 1 on every axis (so a sum fl32(node + u) that rounds up to the next integer at the last node
+ *   is dropped, as in the reference).  Per kept sample, all in fp32 in the reference's order: xi = floor(p), the eight
+ *   corners c = dx*4 + dy*2 + dz, weights ((1-|fx|) * (1-|fy|)) * (1-|fz|), sdf = their weighted sum for c = 0..7;
+ *   gradient = (s4-s0+s5-s1+s6-s2+s7-s3, s2-s0+s3-s1+s6-s4+s7-s5, s1-s0+s3-s2+s5-s4+s7-s6) / (norm + 1e-8).
+ *   Outputs, compacted in candidate order: points [., 3] = half(half(p / (S/2) - 1) * half(shape_scale)), grad [., 3],
+ *   out_sdf [.] (each with room for n_nodes*k samples), *count (device int64) = samples kept.  Order comes from
+ *   ballots and a scan over block counts (ws: ofx_sdf_sample_ws_bytes), never from atomics: with u == NULL the output
+ *   is a pure function of the arguments, bitwise.  n_nodes == 0 launches nothing and writes count 0.  Limits:
+ *   S >= 2, k >= 1, n_nodes * k < 2^31 - 256, depth_start + n_depths <= 31; otherwise OFX_EINVAL.
+ * ofx_sdf_sample_occu: n points; u [n, 3] fp64 or, u == NULL, u_c = (ofx_metrics_hash(seed, shape, i, c) >> 11) * 2^-53.
+ *   pu = u * ((S-1)/S), q = pu * S, trilinear value in fp64 over the fp32 corners (weights as above, the eight
+ *   products summed pairwise).  points [n, 3] = half((pu - 0.5) * 2 * shape_scale); bits [ceil(n/8)] uint8 =
+ *   numpy.packbits(value < 0): point i is bit 7 - i % 8 of byte i / 8, the last byte zero-padded. */
+size_t ofx_sdf_sample_ws_bytes(int64_t n_nodes, int k);
+int ofx_sdf_sample_nodes(const float* sdf, int S, const int32_t* xyz, int64_t n_nodes, const int64_t* depth_off,
+                         int n_depths, int depth_start, int k, uint64_t seed, int64_t shape, const float* u,
+                         float shape_scale, void* ws, uint16_t* points, uint16_t* grad, uint16_t* out_sdf,
+                         int64_t* count, void* stream);
+int ofx_sdf_sample_occu(const float* sdf, int S, int64_t n, uint64_t seed, int64_t shape, const double* u,
+                        float shape_scale, uint16_t* points, uint8_t* bits, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

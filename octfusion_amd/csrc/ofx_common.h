@@ -37,6 +37,15 @@ static inline int ofx_grid(int64_t work_items, int block) {
   return (int)g;
 }
 
+// ---- counter hash of the samplers (ofx_metrics_hash: surface sampling, SDF training samples) ----
+constexpr uint64_t MT_GAMMA = 0x9E3779B97F4A7C15ull;
+__host__ __device__ __forceinline__ uint64_t mt_mix(uint64_t z) {       // splitmix64 finaliser
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+__host__ __device__ __forceinline__ uint64_t mt_step(uint64_t h, uint64_t x) { return mt_mix(h + MT_GAMMA * (x + 1)); }
+
 // ---- Morton codec (x -> bit 3i+2, y -> 3i+1, z -> 3i; batch id in bits 48..) ----
 __host__ __device__ static inline uint32_t ofx_compact3(uint64_t v) {
   // keep every 3rd bit of v (bit 0, 3, 6, ...) and pack them.

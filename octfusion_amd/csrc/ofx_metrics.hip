@@ -27,17 +27,8 @@ namespace {
 
 typedef float f2 __attribute__((ext_vector_type(2)));
 
-// ------------------------------------------------------------------------------------------------ counter hash
-constexpr uint64_t MT_GAMMA = 0x9E3779B97F4A7C15ull;
-
-__host__ __device__ __forceinline__ uint64_t mt_mix(uint64_t z) {       // splitmix64 finaliser
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-__host__ __device__ __forceinline__ uint64_t mt_step(uint64_t h, uint64_t x) { return mt_mix(h + MT_GAMMA * (x + 1)); }
-
 // ------------------------------------------------------------------------------------------------ surface sampling
+// (the counter hash mt_step lives in ofx_common.h: csrc/ofx_sdfdata.hip draws from it too)
 constexpr int SP_T = 1024;                 // prep: one block per shape
 
 // Block-wide inclusive scan of a double in thread order; `total` = the block sum.  All threads must call it.
