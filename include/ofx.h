@@ -833,6 +833,35 @@ int ofx_sdf_sample_nodes(const float* sdf, int S, const int32_t* xyz, int64_t n_
 int ofx_sdf_sample_occu(const float* sdf, int S, int64_t n, uint64_t seed, int64_t shape, const double* u,
                         float shape_scale, uint16_t* points, uint8_t* bits, void* stream);
 
+/* ------------------------------------------------------------------ mesh -> SDF lattice (csrc/ofx_mesh2sdf.hip)
+ * The reference's offline mesh2sdf.compute call (tools/repair_mesh.py:150); tests/mesh2sdf_oracle.py restates the
+ * contract in float64.  `batch` meshes concatenated as for ofx_surface_sample: verts [V, 3] fp32, faces [F, 3] int32,
+ * 0-based into the shape's own vertices; vert_off / tri_off [batch + 1] (int64 device) = where each shape's vertices
+ * and faces begin, the last entry the total.  sdf [batch, S, S, S] fp32, x slowest; lattice point (i, j, k) sits at
+ * p = (2i/S - 1, 2j/S - 1, 2k/S - 1), the convention of ofx_mc_emit with bbmin -1, bbmax 1.  2 <= S <= 512.
+ *   magnitude  |sdf| = the Euclidean distance from p to the nearest point of the nearest triangle, everywhere in the
+ *     lattice: the closest point is evaluated in fp64 and rounded once.  A zero-area triangle is the segment or point
+ *     it is.  Vertices may lie outside [-1, 1]^3.
+ *   sign (signed_ != 0)  negative iff the number of triangles crossed by the ray from p towards -x (crossings with
+ *     x <= x_i) is odd.  A triangle is crossed iff its yz-projection has non-zero area and contains (y, z) moved by
+ *     (eps, eps^2): a zero of an edge function is resolved by -sign(dz), then sign(dy) of the edge, evaluated on one
+ *     ordering of the edge's end points, so a crossing through a shared edge or vertex counts once.  Crossings with
+ *     x < -1 count for the whole column, crossings right of the lattice for none.  signed_ == 0: the distance.
+ *   status [batch] int32: non-zero, and that shape's lattice left unwritten, if a face index is outside [0, V_b) or
+ *     a vertex used by a face is not finite; nothing is read through such an index.  A shape needs >= 1 face (the
+ *     caller checks).
+ *   The output is a pure function of the inputs, bitwise, alone or in a batch: minima and parities do not depend on
+ *   order; atomics only count and assign bin slots.  ws: ofx_mesh_sdf_ws_bytes (0 for arguments out of range:
+ *   batch in [1, 65535], total_verts >= 1, 1 <= total_faces < 2^31).  Bad arguments: OFX_EINVAL, nothing launched. */
+size_t ofx_mesh_sdf_ws_bytes(int batch, int64_t total_verts, int64_t total_faces, int size);
+int ofx_mesh_sdf(const float* verts, const int32_t* faces, const int64_t* vert_off, const int64_t* tri_off, int batch,
+                 int size, int signed_, float* sdf, void* ws, int32_t* status, void* stream);
+/* Measurement aid (tools/mesh2sdf_probe.py; not on the operator path): device pointer to >= 3 zeroed uint64 on the
+ * device the next ofx_mesh_sdf calls run on, NULL (the default): counting off, the plain kernel.  Per brick of 4^3
+ * lattice points the distance pass adds: words[0] += bins searched, words[1] += triangles staged (members of those
+ * bins), words[2] += triangles evaluated after the per-triangle box test (x 64 = point-triangle pairs).  Sticky. */
+int ofx_mesh_sdf_set_counters(unsigned long long* words);
+
 #ifdef __cplusplus
 }
 #endif

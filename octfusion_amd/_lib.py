@@ -175,6 +175,9 @@ _SIGS = {
     'ofx_sdf_sample_nodes': (c_i, [c_p, c_i, c_p, c_l, c_p, c_i, c_i, c_i, c_u64, c_l, c_p, c_f, c_p, c_p, c_p, c_p, c_p,
                                    c_p], True),
     'ofx_sdf_sample_occu': (c_i, [c_p, c_i, c_l, c_u64, c_l, c_p, c_f, c_p, c_p, c_p], True),
+    'ofx_mesh_sdf_ws_bytes': (c_sz, [c_i, c_l, c_l, c_i], False),
+    'ofx_mesh_sdf': (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p], True),
+    'ofx_mesh_sdf_set_counters': (c_i, [c_p], True),
 }
 
 EXPORTS = sorted(_SIGS)
