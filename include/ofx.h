@@ -591,11 +591,22 @@ int ofx_gather_gemm_f32(const float* x, int64_t ldx, int cin, int ntap, int64_t 
 /* A/B knob: 0 keeps sequences of >= 256 tokens on the one-wave-per-32-queries attention kernel (default 1: the keys of a
  * 32-query tile are split over the four waves of a block). */
 int ofx_set_attention_split(int on);
+/* qkv [batch*T, 3*heads*ch] with row pitch ldq >= 3*heads*ch, out [batch*T, heads*ch] with pitch ldo >= heads*ch;
+ * batch, T, heads >= 1 and 1 <= ch <= 128, else OFX_EINVAL with nothing launched.  K and V of one (batch, head) are
+ * staged in LDS at a width CH = ch rounded up to 32, 64 or 128, so a launch is accepted only while
+ *   2 * Tp * (CH + 4) * 4 bytes <= 160 KiB - 2 KiB,  Tp = T rounded up to a multiple of 32:
+ * T <= 544 at ch <= 32, T <= 288 at ch <= 64, T <= 128 at ch <= 128; a longer sequence is OFX_EINVAL.  T >= 256 takes
+ * the split-keys launch (see ofx_set_attention_split).  qkv is read in 16-byte pieces when ch % 4 == 0, ldq % 4 == 0 and
+ * qkv is 16-byte aligned, one float at a time otherwise; the result does not depend on which. */
 int ofx_attention(const float* qkv, int64_t ldq, int batch_size, int T, int heads, int ch,
                   float* out, int64_t ldo, void* stream);
 
 /* Backward of ofx_attention (autograd of QKVAttention, modules.py:538-547): dqkv [rows, 3*C] in the layout of
- * qkv, from dout [rows, C].  rowstat: scratch of batch*heads*T*3 floats.  T <= 512. */
+ * qkv, from dout [rows, C].  rowstat: scratch of batch*heads*T*3 floats.  1 <= T <= 512 (a lane of the query-row
+ * kernel keeps T / 64 <= 8 scores in registers): a longer sequence is OFX_EINVAL with nothing launched, whatever ch is --
+ * narrower than the forward's envelope at ch <= 32 (T <= 544), wider at ch > 32 (forward: T <= 288, then 128).  ch >= 1
+ * has no upper limit here (plain channel loops, no LDS stage per channel), where the forward refuses ch > 128.
+ * Pitches: ldq, ldd >= 3*C, ldo >= C. */
 int ofx_attention_bwd(const float* qkv, int64_t ldq, const float* dout, int64_t ldo, int batch_size, int T, int heads,
                       int ch, float* rowstat, float* dqkv, int64_t ldd, void* stream);
 

@@ -299,6 +299,14 @@ extern "C" int ofx_attention(const float* qkv, int64_t ldq, int batch_size, int 
 // The problem is tiny (T <= 512 tokens, 4 heads, batch 8): two plain fp32 kernels, one wave per query row
 // (row max / sum / D, dQ) and one wave per key row (dK, dV, recomputing P from the saved row statistics);
 // deterministic, no atomics.  Same row layout as the forward kernel.
+
+// The score a * sc, rounded on its own.  The query-row kernel saves the row maximum of these, the key-row kernel forms the same
+// scores again and subtracts it: left to contraction, a * sc - m becomes fma(a, sc, -m) there, the unrounded product minus the
+// rounded one, and the recomputed P is off the saved statistics by an ulp (T = 1: p = 1 + 2^-23 instead of 1, dv != dout).
+__device__ __forceinline__ float score_rounded(float a, float sc) {
+#pragma clang fp contract(off)
+  return a * sc;
+}
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -347,7 +355,7 @@ __global__ void __launch_bounds__(256) attention_bwd_q_kernel(const float* __res
       } else {
         for (int c = 0; c < ch; ++c) { a += qi[c] * kj[c]; d += gi[c] * vj[c]; }
       }
-      s[t] = a * sc; dp[t] = d;
+      s[t] = score_rounded(a, sc); dp[t] = d;
       m = fmaxf(m, s[t]);
     }
   }
@@ -409,7 +417,7 @@ __global__ void __launch_bounds__(256) attention_bwd_kv_kernel(const float* __re
     } else {
       for (int c = 0; c < ch; ++c) { a += qr[c] * kj[c]; d += gr[c] * vj[c]; }
     }
-    const float p = __expf(a * sc - rs[i * 3]) * rs[i * 3 + 1];
+    const float p = __expf(score_rounded(a, sc) - rs[i * 3]) * rs[i * 3 + 1];
     pc[i] = p;
     dc[i] = p * (d - rs[i * 3 + 2]);
   }
