@@ -187,10 +187,16 @@ int ofx_graph_count(const ofx_tree_t* tree, int d, int32_t* seg_cnt, void* strea
 /* pass 2: col[seg_ptr[r*7+dir] ...] = neighbour ids (seg_ptr = excl. scan of seg_cnt). */
 int ofx_graph_fill(const ofx_tree_t* tree, int d, const int32_t* seg_ptr, int32_t* col,
                    void* stream);
-/* CSR -> the reference's COO view: row[e], dir[e] (int64) for edge_idx / edge_dir. */
+/* CSR -> the reference's COO view: row[e], dir[e] (int64) for edge_idx / edge_dir.  Any output may be NULL; col is
+ * required only with col_out. */
 int ofx_graph_expand(const int32_t* seg_ptr, int64_t n_nodes, const int32_t* col,
                      int64_t* row_out, int64_t* col_out, int64_t* dir_out, void* stream);
-/* nbr[r*7+dir] = the single neighbour of segment (r,dir), -1 if none, -2 if several. */
+/* The table builders: ofx_graph_primary / _multi_flag / _primary_ext (declared with the GraphConv tables below),
+ * ofx_graph_type_frac, ofx_graph_reverse_count / _fill, their weighted forms ofx_graph_*_w and the segment-keyed
+ * ofx_seg_*_w.  Every pointer of these is required -- seg_ptr, col, w, rank, node_type and every output, multi_seg
+ * included even when no segment is a multi-neighbour one (pass one spare element): a NULL returns OFX_EINVAL with
+ * nothing launched.
+ * nbr[r*7+dir] = the single neighbour of segment (r,dir), -1 if none, -2 if several. */
 int ofx_graph_primary(const int32_t* seg_ptr, const int32_t* col, int64_t n_nodes, int32_t* nbr,
                       void* stream);
 /* Reverse graph for the backward pass of GraphConv (autograd of index_select + scatter_mean,
@@ -202,7 +208,7 @@ int ofx_graph_reverse_count(const int32_t* seg_ptr, const int32_t* col, int64_t 
 int ofx_graph_reverse_fill(const int32_t* seg_ptr, const int32_t* col, int64_t n_nodes, const int32_t* rev_ptr,
                            int32_t* cursor, int32_t* rev_row, float* rev_w, void* stream);
 /* weighted-graph variants of ofx_graph_primary / _multi_flag / _primary_ext: a segment counts as a single plain
- * source row only if it has one edge of weight exactly 1 */
+ * source row only if it has one edge of weight exactly 1 (pointers: as for the table builders above) */
 int ofx_graph_primary_w(const int32_t* seg_ptr, const int32_t* col, const float* w, int64_t n_nodes, int32_t* nbr,
                         void* stream);
 int ofx_graph_multi_flag_w(const int32_t* seg_ptr, const float* w, int64_t n_nodes, int32_t* flag, void* stream);
@@ -421,7 +427,12 @@ int ofx_graphconv_narrow_in(const float* x, int64_t ldx, int cin, int64_t n_node
  * counts of a multi-neighbour segment): a segment then costs one table entry + one aligned record.  One persistent launch of two
  * 512-thread blocks per CU; a block walks row groups with the next group's gathers in flight under the current
  * group's MFMAs and stores.  Same results as ofx_graphconv_narrow_in to fp32 rounding (the segment means of
- * multi-neighbour segments are taken before, not after, the weight product's inputs are staged: same arithmetic). */
+ * multi-neighbour segments are taken before, not after, the weight product's inputs are staged: same arithmetic).
+ * LIMIT (nt > 0): a record holds the node-type counts of its segment ONE BYTE PER TYPE, so no segment may hold more
+ * than 255 rows of one node type -- a count of 256 reads back as 0 of that type and 1 of the next.  A coarse leaf
+ * across a face from a cell refined four levels deeper has 4^4 = 256 neighbours of one type: the caller must send a
+ * graph depth with a segment above 255 rows to ofx_graphconv_narrow_in (octfusion_amd.ops does, from
+ * DualOctree.max_seg).  Not checked here: the segment sizes live on the device. */
 int ofx_graphconv_narrow_in_tab(const float* x, int64_t ldx, int cin, int64_t n_nodes, const int32_t* seg_ptr,
                                 const int32_t* col, const int32_t* nbr_ext, const int32_t* multi_seg, int64_t n_multi,
                                 void* aux, const uint8_t* node_type, int nt, const float* W, int cout, const float* bias,

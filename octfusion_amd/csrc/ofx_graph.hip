@@ -379,7 +379,7 @@ extern "C" int ofx_graph_multi_flag(const int32_t* seg_ptr, int64_t n_nodes, int
 }
 extern "C" int ofx_graph_primary_ext(const int32_t* seg_ptr, const int32_t* col, int64_t n_nodes, const int32_t* rank,
                                      int32_t* nbr_ext, int32_t* multi_seg, void* stream) {
-  if (!seg_ptr || !col || !rank || !nbr_ext || n_nodes < 0) return OFX_EINVAL;
+  if (!seg_ptr || !col || !rank || !nbr_ext || !multi_seg || n_nodes < 0) return OFX_EINVAL;
   graph_primary_ext_kernel<<<ofx_grid(n_nodes * 7, 256), 256, 0, ofx_stream(stream)>>>(seg_ptr, col, n_nodes * 7,
                                                                                       n_nodes, rank, nbr_ext, multi_seg);
   OFX_LAUNCH_CHECK();
@@ -763,7 +763,10 @@ __global__ void rev_sort_kernel(const int32_t* __restrict__ rev_ptr, int64_t nse
                                 float* __restrict__ rev_w) {
   for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < nseg; s += (int64_t)gridDim.x * blockDim.x) {
     const int32_t a = rev_ptr[s], e = rev_ptr[s + 1];
-    for (int32_t i = a + 1; i < e; ++i) {                    // insertion sort: segments hold <= a handful of edges
+    // insertion sort by one thread, O(n^2): a reverse segment of a dual-octree graph holds one edge per finer
+    // neighbour across a face (4^k: mostly 1 ... 16, 256 four levels apart); a segment structure that is no tree may
+    // hold any number (a thousand entries are a million moves: correct, slow)
+    for (int32_t i = a + 1; i < e; ++i) {
       const int32_t r = rev_row[i];
       const float w = rev_w[i];
       int32_t j = i - 1;
@@ -774,7 +777,7 @@ __global__ void rev_sort_kernel(const int32_t* __restrict__ rev_ptr, int64_t nse
 }
 extern "C" int ofx_graph_reverse_count(const int32_t* seg_ptr, const int32_t* col, int64_t n_nodes, int32_t* rev_cnt,
                                        void* stream) {
-  if (!seg_ptr || !rev_cnt || n_nodes < 0) return OFX_EINVAL;
+  if (!seg_ptr || !col || !rev_cnt || n_nodes < 0) return OFX_EINVAL;
   if (n_nodes == 0) return OFX_OK;
   if (hipMemsetAsync(rev_cnt, 0, (size_t)n_nodes * 7 * sizeof(int32_t), ofx_stream(stream)) != hipSuccess) return OFX_ELAUNCH;
   rev_count_kernel<<<ofx_grid(n_nodes * 7, 256), 256, 0, ofx_stream(stream)>>>(seg_ptr, col, n_nodes * 7, rev_cnt);
@@ -783,7 +786,7 @@ extern "C" int ofx_graph_reverse_count(const int32_t* seg_ptr, const int32_t* co
 }
 extern "C" int ofx_graph_reverse_fill(const int32_t* seg_ptr, const int32_t* col, int64_t n_nodes, const int32_t* rev_ptr,
                                       int32_t* cursor, int32_t* rev_row, float* rev_w, void* stream) {
-  if (!seg_ptr || !rev_ptr || !cursor || !rev_row || !rev_w || n_nodes < 0) return OFX_EINVAL;
+  if (!seg_ptr || !col || !rev_ptr || !cursor || !rev_row || !rev_w || n_nodes < 0) return OFX_EINVAL;
   if (n_nodes == 0) return OFX_OK;
   hipStream_t st = ofx_stream(stream);
   if (hipMemsetAsync(cursor, 0, (size_t)n_nodes * 7 * sizeof(int32_t), st) != hipSuccess) return OFX_ELAUNCH;
@@ -822,21 +825,21 @@ __global__ void graph_primary_ext_w_kernel(const int32_t* __restrict__ seg_ptr, 
 }
 extern "C" int ofx_graph_primary_w(const int32_t* seg_ptr, const int32_t* col, const float* w, int64_t n_nodes,
                                    int32_t* nbr, void* stream) {
-  if (!seg_ptr || !nbr || n_nodes < 0) return OFX_EINVAL;
+  if (!seg_ptr || !col || !w || !nbr || n_nodes < 0) return OFX_EINVAL;
   graph_primary_w_kernel<<<ofx_grid(n_nodes * 7, 256), 256, 0, ofx_stream(stream)>>>(seg_ptr, col, w, n_nodes * 7, nbr);
   OFX_LAUNCH_CHECK();
   return OFX_OK;
 }
 extern "C" int ofx_graph_multi_flag_w(const int32_t* seg_ptr, const float* w, int64_t n_nodes, int32_t* flag,
                                       void* stream) {
-  if (!seg_ptr || !flag || n_nodes < 0) return OFX_EINVAL;
+  if (!seg_ptr || !w || !flag || n_nodes < 0) return OFX_EINVAL;
   graph_multi_flag_w_kernel<<<ofx_grid(n_nodes * 7, 256), 256, 0, ofx_stream(stream)>>>(seg_ptr, w, n_nodes * 7, flag);
   OFX_LAUNCH_CHECK();
   return OFX_OK;
 }
 extern "C" int ofx_graph_primary_ext_w(const int32_t* seg_ptr, const int32_t* col, const float* w, int64_t n_nodes,
                                        const int32_t* rank, int32_t* nbr_ext, int32_t* multi_seg, void* stream) {
-  if (!seg_ptr || !rank || !nbr_ext || n_nodes < 0) return OFX_EINVAL;
+  if (!seg_ptr || !col || !w || !rank || !nbr_ext || !multi_seg || n_nodes < 0) return OFX_EINVAL;
   graph_primary_ext_w_kernel<<<ofx_grid(n_nodes * 7, 256), 256, 0, ofx_stream(stream)>>>(
       seg_ptr, col, w, n_nodes * 7, n_nodes, rank, nbr_ext, multi_seg);
   OFX_LAUNCH_CHECK();
@@ -888,13 +891,13 @@ extern "C" int ofx_table_reverse_fill(const int32_t* nbr, int64_t n_out, int ndi
 }
 extern "C" int ofx_seg_primary_w(const int32_t* seg_ptr, const int32_t* col, const float* w, int64_t nseg, int32_t* nbr,
                                  void* stream) {
-  if (!seg_ptr || !nbr || nseg < 0) return OFX_EINVAL;
+  if (!seg_ptr || !col || !w || !nbr || nseg < 0) return OFX_EINVAL;
   graph_primary_w_kernel<<<ofx_grid(nseg, 256), 256, 0, ofx_stream(stream)>>>(seg_ptr, col, w, nseg, nbr);
   OFX_LAUNCH_CHECK();
   return OFX_OK;
 }
 extern "C" int ofx_seg_multi_flag_w(const int32_t* seg_ptr, const float* w, int64_t nseg, int32_t* flag, void* stream) {
-  if (!seg_ptr || !flag || nseg < 0) return OFX_EINVAL;
+  if (!seg_ptr || !w || !flag || nseg < 0) return OFX_EINVAL;
   graph_multi_flag_w_kernel<<<ofx_grid(nseg, 256), 256, 0, ofx_stream(stream)>>>(seg_ptr, w, nseg, flag);
   OFX_LAUNCH_CHECK();
   return OFX_OK;
@@ -902,7 +905,7 @@ extern "C" int ofx_seg_multi_flag_w(const int32_t* seg_ptr, const float* w, int6
 extern "C" int ofx_seg_primary_ext_w(const int32_t* seg_ptr, const int32_t* col, const float* w, int64_t nseg,
                                      int64_t n_src, const int32_t* rank, int32_t* nbr_ext, int32_t* multi_seg,
                                      void* stream) {
-  if (!seg_ptr || !rank || !nbr_ext || nseg < 0) return OFX_EINVAL;
+  if (!seg_ptr || !col || !w || !rank || !nbr_ext || !multi_seg || nseg < 0) return OFX_EINVAL;
   graph_primary_ext_w_kernel<<<ofx_grid(nseg, 256), 256, 0, ofx_stream(stream)>>>(seg_ptr, col, w, nseg, n_src, rank,
                                                                                 nbr_ext, multi_seg);
   OFX_LAUNCH_CHECK();

@@ -223,7 +223,9 @@ __global__ void __launch_bounds__(256) narrow_rec_aux_kernel(const float* __rest
   const int64_t sgm = multi_seg[v];
   const int32_t b = seg_ptr[sgm], e = seg_ptr[sgm + 1];
   // groups of four neighbours with all column ids, then all x pieces and node types in flight together (a serial walk is
-  // a chain of two dependent loads per neighbour; segments hold 4 ... 16 of them)
+  // a chain of two dependent loads per neighbour).  A segment holds 4^k neighbours where a leaf faces a cell refined k
+  // levels deeper: 4 ... 16 on the shell trees, up to 256 at k = 4 -- one thread walks them all, and the byte-wide type
+  // counters t0 / t1 below hold at most 255 of one type (the caller keeps longer segments away: include/ofx.h)
   for (int32_t p0 = b; p0 < e; p0 += 4) {
     int64_t j[4];
 #pragma unroll

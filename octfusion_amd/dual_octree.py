@@ -96,6 +96,7 @@ class DualOctree:
         self._rev = {}
         self._bid32 = {}
         self._count = {}
+        self._max_seg = {}
         self._tf = {}
         self._maps = {}
         self._ntype8 = {}
@@ -131,7 +132,7 @@ class DualOctree:
         return top if top >= self.full_depth else self.full_depth - 1
 
     def _adopt(self, prev, d, unpool_ok):
-        for name in ('_csr', '_nbr', '_ext', '_bid32', '_ntype8', 'batch_id_dict', '_count'):
+        for name in ('_csr', '_nbr', '_ext', '_bid32', '_ntype8', 'batch_id_dict', '_count', '_max_seg'):
             getattr(self, name)[d] = getattr(prev, name)[d]
         for key, v in prev._ext.items():                # aux plans of the adopted depth (keyed ('aux_plan', d, rows) / ('oct_plan', d, shift))
             if isinstance(key, tuple) and key[0] in ('aux_plan', 'oct_plan') and key[1] == d:
@@ -157,13 +158,15 @@ class DualOctree:
         seg_ptr = torch.empty(N * 7 + 1, dtype=torch.int32, device=dev)
         ws = torch.empty(_lib.lib().ofx_scan_ws_bytes(N * 7), dtype=torch.uint8, device=dev)
         call('ofx_scan_i32', ptr(seg_cnt), ptr(seg_ptr), N * 7, ptr(ws), stream())
-        # the multi-neighbour ranks only need the segment sizes, so both totals (edges, multi-neighbour segments)
-        # come back in ONE host read per depth -- they size the column array and the pre-averaged-row scratch
+        # the multi-neighbour ranks only need the segment sizes, so the totals (edges, multi-neighbour segments) and the
+        # largest segment come back in ONE host read per depth -- they size the column array and the pre-averaged-row
+        # scratch; the largest segment decides whether byte-wide per-type counters can hold this depth (max_seg)
+        seg_max = seg_cnt.max()                         # (before the flags overwrite the sizes)
         flag = seg_cnt
         call('ofx_graph_multi_flag', ptr(seg_ptr), N, ptr(flag), stream())
         rank = torch.empty(N * 7 + 1, dtype=torch.int32, device=dev)
         call('ofx_scan_i32', ptr(flag), ptr(rank), N * 7, ptr(ws), stream())
-        E, V = torch.stack([seg_ptr[-1], rank[-1]]).tolist()
+        E, V, self._max_seg[d] = torch.stack([seg_ptr[-1], rank[-1], seg_max]).tolist()
         col = torch.empty(E, dtype=torch.int32, device=dev)
         call('ofx_graph_fill', tree, d, ptr(seg_ptr), ptr(col), stream())
         bid = torch.empty(N, dtype=torch.int32, device=dev)
@@ -250,6 +253,11 @@ class DualOctree:
     def ext(self, d):
         """(nbr_ext int32 [N*7], multi_seg int32 [V], V): the branch-free gather table (ofx.h)."""
         return self._ext[d]
+
+    def max_seg(self, d):
+        """rows in the largest (row, dir) segment of graph depth d: 4^k where a leaf faces a cell refined k levels deeper,
+        256 from k = 4 on -- more than the byte-wide node-type counters of ofx_graphconv_narrow_in_tab hold (ofx.h)."""
+        return self._max_seg[d]
 
     def aux_plan(self, d, rows_per_block=None):
         """(plan int32, leftover count) for ofx_gn_apply_planes: which 64-row block of the GroupNorm launch writes which

@@ -97,7 +97,7 @@ class GraphConv(nn.Module):
                 y = ops.graphconv_narrow_in(x, seg_ptr, col, self.weights, self.in_channels, nt,
                                             doctree.node_type8(d) if nt else None, self.bias if self.use_bias else None,
                                             doctree.batch_id32(d) if stats is not None else None, out, stats,
-                                            ext=doctree.ext(d))
+                                            ext=doctree.ext(d), max_seg=doctree.max_seg(d))
                 if stats is not None:
                     setattr(y, ops.STATS_ATTR, stats)
                 return y

@@ -709,11 +709,16 @@ NARROW_IN_TAB = os.environ.get('OFX_NARROW_IN_TAB', '1') == '1'
 NARROW_IN_TAB_MIN_ROWS = int(os.environ.get('OFX_NARROW_IN_TAB_MIN_ROWS', str(1 << 19)))
 
 
+NARROW_IN_TAB_MAX_SEG = 255      # one byte per node type in a record of the table-driven launch (include/ofx.h)
+
+
 def graphconv_narrow_in(x, seg_ptr, col, weights, cin, nt, node_type=None, bias=None, batch_id=None, out=None, stats=None,
-                        ext=None):
+                        ext=None, max_seg=None):
     """The U-Net's INPUT GraphConv (3 / 8 channels -> 64 / 128): gather + exact-fp32 FMA with the weights in registers
     (ofx_graphconv_narrow_in).  weights: the raw nn.Parameter [7 * (cin + nt), cout]; node_type: uint8 [N].
-    ext = (nbr_ext, multi_seg, n_multi): the branch-free gather table -> the persistent, pipelined launch."""
+    ext = (nbr_ext, multi_seg, n_multi): the branch-free gather table -> the persistent, pipelined launch, taken only
+    when the caller vouches with `max_seg` (DualOctree.max_seg) that no segment holds more than NARROW_IN_TAB_MAX_SEG
+    rows: beyond that the launch's byte-wide node-type counters wrap, and the CSR-walking launch takes the layer."""
     x, ldx = _row_major(x)
     w = weights.detach()
     if not w.is_contiguous():
@@ -734,7 +739,8 @@ def graphconv_narrow_in(x, seg_ptr, col, weights, cin, nt, node_type=None, bias=
     with _layer_bracket(flops, nbytes, cout, ('graph', N, cin, cout)):
         ws = workspace(x.device)
         _meta('graphconv_narrow', flops, nbytes, (N, cin, cout, 'narrow_in'))
-        if ext is not None and NARROW_IN_TAB and N >= NARROW_IN_TAB_MIN_ROWS:
+        if (ext is not None and NARROW_IN_TAB and N >= NARROW_IN_TAB_MIN_ROWS and max_seg is not None and
+                (max_seg <= NARROW_IN_TAB_MAX_SEG or not nt)):
             nbr_ext, multi_seg, n_multi = ext
             aux = torch.empty((N + n_multi + 1) * (8 if cin <= 4 else 16), dtype=torch.float32, device=x.device)
             call('ofx_graphconv_narrow_in_tab', ptr(x), ldx, cin, N, ptr(seg_ptr), ptr(col), ptr(nbr_ext), ptr(multi_seg),

@@ -675,6 +675,89 @@ def test_graphconv_backward_with_an_empty_batch_element():
     assert n == 6
 
 
+@functools.lru_cache(maxsize=None)
+def _deep_oracle_case(kind, cin, cout, nt):
+    """float64 oracle of one GraphConv layer on a deep tree of tests/graph_oracle.py, depth 6: forward, and dx / dW by
+    torch.autograd of oracle.modules.graph_conv -- once per case, shared by the launches below."""
+    import graph_oracle as G
+    from oracle import modules as OM
+    o_doc = G.tree(kind)[1]
+    d = o_doc.depth
+    N = int(o_doc.graph[d]['node_type'].shape[0])
+    tag = '%s_%d_%d' % (kind, cin, cout)
+    x = C.rand_input('dx_%s' % tag, N, cin)
+    dy = C.rand_input('ddy_%s' % tag, N, cout)
+    W = _weights('dw_%s' % tag, cin, nt, cout)
+    with torch.enable_grad():
+        x64 = x.double().requires_grad_(True)
+        W64 = W.double().requires_grad_(True)
+        y = OM.graph_conv(x64, o_doc, d, W64, None, nt)
+        (y * dy.double()).sum().backward()
+    return dict(x=x, dy=dy, W=W, ref=y.detach(), dx=x64.grad, dW=W64.grad, d=d, N=N)
+
+
+@pytest.mark.parametrize('kind', ['deep_a', 'full_face'])
+@pytest.mark.parametrize('cin,cout', [(32, 64), (96, 128)])
+def test_graphconv_on_deep_trees(kind, cin, cout):
+    """Every GraphConv launch on trees four levels deeper than their full layer (`deep_a`: segments of up to 91 rows
+    over many blocks; `full_face`: nine segments of 256 rows), depth 6, against oracle.modules.graph_conv in float64:
+    ofx_graphconv_fwd by its col path (no gather table) and its fast path, the planes kernel as persistent stream-K
+    launch and as one tile per block, and ops.graphconv_backward's dx / dW against the oracle's autograd, run twice
+    (determinism).  Bounds: the ones this file and tests/test_gpu_persistent.py use for the same entry points in the
+    default precision -- dx as `_layer` judges it: against the figure of torch's own fp32 contraction on the CPU
+    (`_within`), dW 5e-5."""
+    import graph_oracle as G
+    from octfusion_amd import _lib, modules as M, octree as PO, ops
+    from octfusion_amd.dual_octree import DualOctree
+    nt = 5
+    K = _deep_oracle_case(kind, cin, cout, nt)
+    d, N = K['d'], K['N']
+    doc = DualOctree(G.build_tree(kind, PO, dev()))
+    seg_ptr, col, n_rows, _ = doc.csr(d)
+    assert n_rows == N and doc.max_seg(d) == (256 if kind == 'full_face' else 91)
+    assert ops.get_precision() == ops.DEFAULT_PRECISION
+    xg, dyg, Wg = K['x'].to(dev()), K['dy'].to(dev()), K['W'].to(dev())
+    # ofx_graphconv_fwd: col path (no table), fast path (branch-free gather through nbr_ext + aux rows)
+    pw = ops.PackedWeight().get(Wg, 'graphconv', cin, nt)
+    tf = doc.type_frac(d, nt)
+    for path, ext in (('col', None), ('fast', doc.ext(d))):
+        y = ops.graphconv(xg, doc.nbr(d), seg_ptr, col, pw, cin, tf, ext=ext)
+        e = _rel(y, K['ref'])
+        print('ofx_graphconv_fwd', kind, cin, cout, path, e)
+        assert e <= 5e-5, (path, e)
+    # the planes kernel through the module, both launch shapes
+    conv = M.GraphConv(cin, cout, 7, 7, nt)
+    conv.load_state_dict({'weights': K['W']})
+    conv = conv.to(dev())
+    saved = ops.PLANES_MIN_TILES
+    ops.PLANES_MIN_TILES = 1
+    try:
+        for persistent in (1, 0):
+            _lib.call('ofx_set_gconv_persistent', persistent)
+            xp = ops.planes_split(xg, conv.planes_mode(doc, d))
+            assert ops.planes_of(xp) == ops.planes_mode() != 0
+            y = conv(xp, doc, d)
+            torch.cuda.synchronize()
+            assert not ops.sync_error(dev()), 'a flag wait of the persistent launch gave up'
+            e = _rel(y, K['ref'])
+            print('planes GraphConv', kind, cin, cout, 'persistent' if persistent else 'tile per block', e)
+            assert e <= 2e-5, (persistent, e)
+    finally:
+        ops.PLANES_MIN_TILES = saved
+        _lib.call('ofx_set_gconv_persistent', 1)
+    # backward against the oracle's autograd
+    dx, dW = ops.graphconv_backward(xg, dyg, doc, d, Wg, nt)
+    dx2, dW2 = ops.graphconv_backward(xg, dyg, doc, d, Wg, nt)
+    assert torch.equal(dW, dW2), 'dW is not deterministic'
+    assert torch.equal(dx, dx2), 'dx is not deterministic'
+    o_doc = G.tree(kind)[1]
+    floor = errors(_gconv_dx_ref(o_doc, d, K['dy'], K['W'], cin, nt, torch.float32), K['dx'])
+    e, ew = errors(dx.cpu(), K['dx']), errors(dW, K['dW'])
+    print('graphconv_backward', kind, cin, cout, 'dx', e, 'fp32 floor', floor, 'dW', ew)
+    _within(e, floor, ('dx', kind, cin, cout))
+    assert ew['rel_to_max'] <= 5e-5, ('dW', kind, cin, cout, ew)
+
+
 def test_group_norm_backward_real_widths():
     """ofx_gn_backward at C = 256 / 512 / 768, 32 groups, ragged B = 8 (one element empty below the full layer)."""
     import torch.nn.functional as F

@@ -8,7 +8,10 @@
     planes over the CSR, for the rows owned by an octet AND the leftovers, and against the two older launches;
   * ragged batch with an empty element (leaf prefix not a multiple of eight: shift != 0, octets that straddle batch
     elements and the start / end of the tensor), every width class of the thread mapping (C / 4 lanes per row: 16, 24,
-    32, 48, 96, 128 -> 16 ... 2 octets per block, incl. widths that leave lanes idle), the three operand formats.
+    32, 48, 96, 128 -> 16 ... 2 octets per block, incl. widths that leave lanes idle), the three operand formats;
+  * trees four levels deeper than their full layer (tests/graph_oracle.py): `deep` (deep_b: an empty first element, aux
+    rows that average up to 91 sources spread over many octets and 64-row blocks) and `full_face` (every aux row averages
+    256 sources: all nine are leftovers of both plans).
 """
 import pytest
 import torch
@@ -24,6 +27,11 @@ def _tree(kind):
     from octfusion_amd.dual_octree import DualOctree
     from octfusion_amd.octree import split2octree_small
     from oracle import dual_octree as OD, sampler as OS
+    if kind in ('deep', 'full_face'):
+        import graph_oracle as G
+        from octfusion_amd import octree as PO
+        name = 'deep_b' if kind == 'deep' else kind
+        return DualOctree(G.build_tree(name, PO, dev())), G.tree(name)[1]
     if kind == 'ragged':
         split = C.random_split_small(5, 3, 17, p=0.45)
         split[1] = -1.0                                   # an element with nothing below the full layer
@@ -97,7 +105,8 @@ def _check_launches(outs, ref, doc, d, Cc, mode, need_both=True):
 @pytest.mark.parametrize('kind,d,Cc,mode', [('ragged', 5, 128, 3), ('ragged', 5, 64, 3), ('ragged', 4, 96, 3),
                                             ('ragged', 5, 192, 2), ('ragged', 4, 384, 3), ('ragged', 5, 512, 3),
                                             ('ragged', 5, 128, 1), ('shell', 6, 128, 3), ('shell', 5, 256, 3),
-                                            ('shell', 6, 64, 2)])
+                                            ('shell', 6, 64, 2), ('deep', 6, 128, 3), ('deep', 5, 96, 3),
+                                            ('deep', 6, 64, 2), ('full_face', 6, 128, 3), ('full_face', 6, 64, 2)])
 def test_octet_launch_matches_the_older_launches_and_the_oracle(kind, d, Cc, mode):
     from octfusion_amd import modules as M, ops
     from oracle import modules as OM
@@ -128,6 +137,11 @@ def test_octet_launch_matches_the_older_launches_and_the_oracle(kind, d, Cc, mod
     finally:
         ops.AUX_PLAN, ops.GN_OCT_FINALIZE_MAX_ELEMS = saved
         ops.GN_OCT_FINALIZE = True
+    if kind in ('deep', 'full_face'):
+        lens = (seg_ptr[multi_seg[:V].long() + 1] - seg_ptr[multi_seg[:V].long()])
+        assert int(lens.max()) >= (256 if kind == 'full_face' else (64 if d == 6 else 16)), int(lens.max())
+        if kind == 'full_face':                                    # nine aux rows of 256 sources, none owned by a block
+            assert V == 9 and plan.n_own == 0 and bool((lens == 256).all())
     _check_launches(outs, ref, doc, d, Cc, mode)
 
 
