@@ -276,6 +276,33 @@ int ofx_gridconv_bwd_weight(const float* x, int64_t ldx, int cin, int64_t n_in, 
 int ofx_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
                    float beta1, float beta2, float eps, float weight_decay, int step, void* stream);
 int ofx_ema_update(float* ema, const float* param, int64_t n, float beta, void* stream);
+/* The same two updates for a whole list of tensors in a handful of launches (csrc/ofx_train.hip; the per-element
+ * arithmetic is shared with the two entry points above, so the results are the same bits).  rows: a HOST array, read
+ * before the call returns.  Per row: grad == NULL: no AdamW and no decay (torch's grad=None rule), EMA only;
+ * ema == NULL: AdamW only; n == 0: skipped.  param / grad / moments / ema need no alignment (16-byte aligned rows take
+ * the vector path).  The EMA reads the freshly updated parameter.  OFX_EINVAL: n < 0, step < 1, a NULL param with
+ * n > 0, a gradient without both moments.  Nothing is launched when an argument is invalid. */
+typedef struct OfxAdamRow {
+  float* param;
+  const float* grad;
+  float* exp_avg;
+  float* exp_avg_sq;
+  float* ema;
+  int64_t n;
+} OfxAdamRow;
+int ofx_adamw_ema_multi(const OfxAdamRow* rows, int64_t n_rows, float lr, float beta1, float beta2, float eps,
+                        float weight_decay, int step, float ema_beta, void* stream);
+/* Elements per work chunk of ofx_adamw_ema_multi (a row of n elements is cut into ceil(n / chunk) chunks). */
+int ofx_adamw_ema_multi_chunk(void);
+/* Rows per launch of ofx_adamw_ema_multi: a call over R rows with work launches ceil(R / rows) kernels (one more where
+ * a slab would exceed 2^30 chunks). */
+int ofx_adamw_ema_multi_rows(void);
+/* MSE loss of the diffusion stages and its gradient without a host read: dy[i] = (y[i] - target[i]) * (float)(2.0 / n),
+ * *loss_out (device double) = mean((double)diff * diff) with diff the fp32 difference.  partials: device workspace of
+ * ofx_mse_grad_partials(n) doubles; the sum runs in a fixed order (no atomics): the same bits run to run.  n >= 1. */
+int64_t ofx_mse_grad_partials(int64_t n);
+int ofx_mse_grad(const float* y, const float* target, float* dy, double* partials, double* loss_out, int64_t n,
+                 void* stream);
 /* NeuralMPU SDF evaluation -- replaces NeuralMPU.__call__ / get_linear_pred / octree_linear_pts
  * (models/networks/dualoctree_networks/mpu.py:55-153), spmm / modulated_spmm (utils/spmm.py:12-61) and, with the
  * _grid entry, the sampling loop of calc_sdf (utils/util_dualoctree.py:99-118).

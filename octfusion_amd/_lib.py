@@ -26,6 +26,10 @@ class OfxTree(ctypes.Structure):
                 ('nnum_host', c_p), ('nnum_nempty_host', c_p)]
 
 
+class OfxAdamRow(ctypes.Structure):
+    _fields_ = [('param', c_p), ('grad', c_p), ('exp_avg', c_p), ('exp_avg_sq', c_p), ('ema', c_p), ('n', c_l)]
+
+
 # name -> (restype, argtypes, returns_status)
 _SIGS = {
     'ofx_version': (c_i, [], False),
@@ -76,6 +80,11 @@ _SIGS = {
     'ofx_attention_bwd': (c_i, [c_p, c_l, c_p, c_l, c_i, c_i, c_i, c_i, c_p, c_p, c_l, c_p], True),
     'ofx_adamw_step': (c_i, [c_p, c_p, c_p, c_p, c_l, c_f, c_f, c_f, c_f, c_f, c_i, c_p], True),
     'ofx_ema_update': (c_i, [c_p, c_p, c_l, c_f, c_p], True),
+    'ofx_adamw_ema_multi': (c_i, [c_p, c_l, c_f, c_f, c_f, c_f, c_f, c_i, c_f, c_p], True),
+    'ofx_adamw_ema_multi_chunk': (c_i, [], False),
+    'ofx_adamw_ema_multi_rows': (c_i, [], False),
+    'ofx_mse_grad_partials': (c_l, [c_l], False),
+    'ofx_mse_grad': (c_i, [c_p, c_p, c_p, c_p, c_p, c_l, c_p], True),
     'ofx_gn_fused_rows': (c_i, [c_p, c_l, c_i, c_i, c_i, c_i, c_f, c_f, c_p, c_p, c_i, c_p, c_l, c_p], True),
     'ofx_set_gn_rows16': (c_i, [c_i], True),
     'ofx_mpu_eval': (c_i, [ctypes.POINTER(OfxTree), c_i, c_i, c_p, c_l, c_p, c_p, c_p, c_p], True),

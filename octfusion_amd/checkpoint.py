@@ -46,10 +46,12 @@ def load_ckpt(ckpt, df, ema_df=None, load_options=STAGE_NETS, opt=None, allow_pi
     return sd.get('global_step')
 
 
-def save_ckpt(path, df, ema_df, global_step, stage_flag='hr', opt_state=None):
+def save_ckpt(path, df, ema_df, global_step, stage_flag='hr', opt_state=None, extra=None):
     """octfusion_model_union.py:501-523 / octfusion_model_union_3t.py:219-229 (file layout only; rotation of old
-    files is the trainer's business): the nets of every stage up to `stage_flag`."""
+    files is the trainer's business): the nets of every stage up to `stage_flag`.  extra: further top-level keys (the
+    training driver's 'train_state'; the reference's loader reads the keys it knows and ignores the rest)."""
     sd = {'opt': opt_state if opt_state is not None else {}, 'global_step': global_step}
+    sd.update(extra or {})
     for name in STAGE_NETS[:_STAGES_UP_TO[stage_flag]]:
         sd['df_' + name] = getattr(df, name).state_dict()
         sd['ema_df_' + name] = getattr(ema_df, name).state_dict()

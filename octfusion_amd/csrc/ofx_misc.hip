@@ -1,6 +1,7 @@
 // libofx: glue kernels (row permutations for pool/unpool, embeddings, DDIM updates),
 // status strings, device check.  All HBM-bound elementwise work.
 #include "ofx_gemm_common.h"     // (ofx_common.h + the 16-bit operand-pair helpers: ofx_rows_copy_planes)
+#include "ofx_optim.h"
 
 extern "C" int ofx_version(void) { return 1; }
 
@@ -299,18 +300,16 @@ extern "C" int ofx_ddim_x0_update(float* x, const float* x0, const float* noise,
 // ---------------------------------------------------------------------------------
 // Optimiser side of the training step (reference octfusion_model_union.py:142, 478-487): torch.optim.AdamW's
 // update (decoupled weight decay, bias-corrected moments) and the EMA of the weights
-// (ldm_diffusion_util.py:38-54: old * beta + (1 - beta) * new), one elementwise pass each.
+// (ldm_diffusion_util.py:38-54: old * beta + (1 - beta) * new), one elementwise pass each.  The arithmetic lives in
+// ofx_optim.h, shared with the multi-tensor step of ofx_train.hip.
 __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                              float* __restrict__ v, int64_t n, float lr, float b1, float b2, float eps, float wd,
                              float bc1, float bc2) {
+  const OfxAdamW a = ofx_adamw_setup(lr, b1, b2, eps, wd, bc1, bc2);
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const float gi = g[i];
-    float pi = p[i] * (1.f - lr * wd);
-    const float mi = b1 * m[i] + (1.f - b1) * gi;
-    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+    float mi = m[i], vi = v[i];
+    const float pi = ofx_adamw_elem(a, p[i], g[i], mi, vi);
     m[i] = mi; v[i] = vi;
-    const float denom = sqrtf(vi) / sqrtf(bc2) + eps;
-    pi -= (lr / bc1) * (mi / denom);
     p[i] = pi;
   }
 }
@@ -326,7 +325,7 @@ extern "C" int ofx_adamw_step(float* param, const float* grad, float* exp_avg, f
 }
 __global__ void ema_kernel(float* __restrict__ e, const float* __restrict__ p, int64_t n, float beta) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    e[i] = e[i] * beta + (1.f - beta) * p[i];
+    e[i] = ofx_ema_elem(e[i], p[i], beta);
 }
 extern "C" int ofx_ema_update(float* ema, const float* param, int64_t n, float beta, void* stream) {
   if (n < 0 || (n > 0 && (!ema || !param))) return OFX_EINVAL;

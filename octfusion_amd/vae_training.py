@@ -288,9 +288,11 @@ def poly_lr(base_lr, epoch, epochs, power=0.9):
 
 
 @torch.no_grad()
-def vae_stage_step(vae, opt, data, doctree_in, doctree_out, pos, sdf_gt, grad_gt, noise=None, kl_weight=1.0):
+def vae_stage_step(vae, opt, data, doctree_in, doctree_out, pos, sdf_gt, grad_gt, noise=None, kl_weight=1.0,
+                   fused=False):
     """One optimisation step of the VAE (octfusion_model_vae.py:255-262).  opt: training.AdamW over
-    vae.named_parameters().  Returns the dict of losses (0-d device tensors)."""
+    vae.named_parameters().  Returns the dict of losses (0-d device tensors).  fused: the optimiser step is one
+    multi-tensor call (AdamW.step(fused=True)) instead of a launch per parameter."""
     losses, _, grads = vae_forward_backward(vae, data, doctree_in, doctree_out, pos, sdf_gt, grad_gt, noise, kl_weight)
-    opt.step(grads)
+    opt.step(grads, fused=fused)
     return losses
