@@ -542,6 +542,27 @@ int ofx_gn_apply_planes_oct(const float* x, int64_t ldx, int64_t n, int C, const
                             int64_t ldo_bytes, int64_t n_multi, void* aux, const int32_t* oct_ptr,
                             const int32_t* oct_ent, int64_t n_own, int shift, const int32_t* left_head,
                             const int32_t* left_src, int64_t n_left, void* stream);
+/* Channel windows: ofx_gn_apply_planes / ofx_gn_apply_planes_oct / ofx_gn_finalize on the channels [c_lo, c_hi) of
+ * the [n, C] tensor.  Every other argument is that of the full call (x, w, bias, mean, rstd, sums, out and aux are the
+ * FULL tensor's pointers, groups the full tensor's group count): the launch writes the 128-B plane lines of the
+ * window's chunks and the window's part of every aux row (aux pitch = ldo_bytes), reads the sums / mean / rstd of the
+ * window's groups only, and computes every element exactly as the full call does -- so the calls on [c_lo, C) and
+ * [0, c_lo) together leave the bytes of one full call.  c_lo and c_hi must be multiples of 32 (64 in mode 1) and of
+ * C / groups, 0 <= c_lo < c_hi <= C: anything else is OFX_EINVAL. */
+int ofx_gn_finalize_window(const double* sums, const float* count, int batch_size, int C, int groups, int c_lo,
+                           int c_hi, float eps, float count_eps, float* mean, float* rstd, void* stream);
+int ofx_gn_apply_planes_window(const float* x, int64_t ldx, int64_t n, int C, int c_lo, int c_hi,
+                               const int32_t* batch_id, const float* mean, const float* rstd, const double* sums,
+                               const float* count, int groups, float eps, float count_eps, const float* w,
+                               const float* bias, int act, int mode, void* out, int64_t ldo_bytes,
+                               const int32_t* seg_ptr, const int32_t* col, const int32_t* multi_seg, int64_t n_multi,
+                               void* aux, const int32_t* aux_plan, int64_t aux_left, void* stream);
+int ofx_gn_apply_planes_oct_window(const float* x, int64_t ldx, int64_t n, int C, int c_lo, int c_hi,
+                                   const int32_t* batch_id, const float* mean, const float* rstd, const double* sums,
+                                   const float* count, int groups, float eps, float count_eps, const float* w,
+                                   const float* bias, int act, int mode, void* out, int64_t ldo_bytes, int64_t n_multi,
+                                   void* aux, const int32_t* oct_ptr, const int32_t* oct_ent, int64_t n_own, int shift,
+                                   const int32_t* left_head, const int32_t* left_src, int64_t n_left, void* stream);
 /* rows per main block of ofx_gn_apply_planes: the granularity `aux_plan` is built for (the host-side plan builder,
  * octfusion_amd/dual_octree.py aux_plan, asks instead of assuming). */
 int ofx_gn_apply_rows(void);
@@ -556,6 +577,18 @@ int ofx_graphconv_fwd_planes(const void* xp, int64_t ldx_bytes, int cin, int64_t
                              const float* res, int64_t ldr, float* out, int64_t ldc, double* stats /* optional */,
                              int64_t stats_ld, void* ws, size_t ws_bytes, void* sync /* optional */, size_t sync_bytes,
                              int mode, int aux_ready, void* stream);
+/* ofx_graphconv_fwd_planes with the number of compute units THIS launch's persistent schedule is planned for: 0 = the
+ * process-wide value (ofx_set_gconv_cus), > 0 = that many whatever the process-wide value is (clamped to the device's
+ * count; 1..7: OFX_EINVAL).  A launch planned for a subset leaves the other units to kernels on other streams -- and,
+ * unlike the process-wide setter, says so per launch: "this stream 128, that stream all" inside one captured step. */
+int ofx_graphconv_fwd_planes_cus(const void* xp, int64_t ldx_bytes, int cin, int64_t n_nodes, const int32_t* seg_ptr,
+                                 const int32_t* col, const int32_t* nbr_ext, const int32_t* multi_seg, int64_t n_multi,
+                                 void* aux, size_t aux_bytes, const void* tfp, int64_t ldt_bytes, int nt,
+                                 const void* W2, int cout, const float* bias, const float* emb, int64_t lde,
+                                 const int32_t* batch_id, const float* res, int64_t ldr, float* out, int64_t ldc,
+                                 double* stats /* optional */, int64_t stats_ld, void* ws, size_t ws_bytes,
+                                 void* sync /* optional */, size_t sync_bytes, int mode, int aux_ready, int cus,
+                                 void* stream);
 /* 1 (default): persistent launch (whole-tile rounds + a stream-K region) where the shape qualifies; 0: always one tile
  * per block; 2: persistent with pure stream-K (no whole-tile rounds) -- A/B knob, same values.  Anything else:
  * OFX_EINVAL. */

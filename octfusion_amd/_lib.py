@@ -130,6 +130,15 @@ _SIGS = {
     'ofx_graphconv_fwd_planes': (c_i, [c_p, c_l, c_i, c_l, c_p, c_p, c_p, c_p, c_l, c_p, c_sz, c_p, c_l, c_i, c_p, c_i,
                                        c_p, c_p, c_l, c_p, c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_sz, c_p, c_sz, c_i, c_i,
                                        c_p], True),
+    'ofx_graphconv_fwd_planes_cus': (c_i, [c_p, c_l, c_i, c_l, c_p, c_p, c_p, c_p, c_l, c_p, c_sz, c_p, c_l, c_i, c_p,
+                                           c_i, c_p, c_p, c_l, c_p, c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_sz, c_p, c_sz,
+                                           c_i, c_i, c_i, c_p], True),
+    'ofx_gn_finalize_window': (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_p, c_p, c_p], True),
+    'ofx_gn_apply_planes_window': (c_i, [c_p, c_l, c_l, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_f, c_f, c_p, c_p,
+                                         c_i, c_i, c_p, c_l, c_p, c_p, c_p, c_l, c_p, c_p, c_l, c_p], True),
+    'ofx_gn_apply_planes_oct_window': (c_i, [c_p, c_l, c_l, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_f, c_f, c_p,
+                                             c_p, c_i, c_i, c_p, c_l, c_l, c_p, c_p, c_p, c_l, c_i, c_p, c_p, c_l, c_p],
+                                       True),
     'ofx_set_gconv_persistent': (c_i, [c_i], True),
     'ofx_set_gconv_cus': (c_i, [c_i], True),
     'ofx_gemm_planes_packed_bytes': (c_l, [c_i, c_i, c_i], False),

@@ -674,7 +674,7 @@ static int g3_auto_wm(int64_t M, int cout, int nkt, int ni) {
 }
 // persistent stream-K kernel (ofx_gemm3.hip); returns 1 when the shape / workspace does not qualify
 int ofx_launch_gconv3(Gemm2Args& a, int mode, int wm, int ni, void* ws_tail, size_t ws_tail_bytes, void* sync,
-                      size_t sync_bytes, hipStream_t st, int nd = 7);
+                      size_t sync_bytes, hipStream_t st, int nd = 7, int cus = 0);
 static int g2_persistent = 1;               // 1 (default): persistent stream-K blocks where the shape qualifies
 void ofx_gconv3_set_hybrid(int on);          // ofx_gemm3.hip
 extern "C" int ofx_set_gconv_persistent(int on) {
@@ -684,15 +684,15 @@ extern "C" int ofx_set_gconv_persistent(int on) {
   return OFX_OK;
 }
 
-extern "C" int ofx_graphconv_fwd_planes(const void* xp, int64_t ldx_bytes, int cin, int64_t n_nodes,
-                                        const int32_t* seg_ptr, const int32_t* col, const int32_t* nbr_ext,
-                                        const int32_t* multi_seg, int64_t n_multi, void* aux, size_t aux_bytes,
-                                        const void* tfp, int64_t ldt_bytes, int nt, const void* W2, int cout,
-                                        const float* bias, const float* emb, int64_t lde, const int32_t* batch_id,
-                                        const float* res, int64_t ldr, float* out, int64_t ldc, double* stats,
-                                        int64_t stats_ld, void* ws, size_t ws_bytes, void* sync, size_t sync_bytes,
-                                        int mode, int aux_ready, void* stream) {
-  if (mode < 1 || mode > 3) return OFX_EINVAL;
+extern "C" int ofx_graphconv_fwd_planes_cus(const void* xp, int64_t ldx_bytes, int cin, int64_t n_nodes,
+                                            const int32_t* seg_ptr, const int32_t* col, const int32_t* nbr_ext,
+                                            const int32_t* multi_seg, int64_t n_multi, void* aux, size_t aux_bytes,
+                                            const void* tfp, int64_t ldt_bytes, int nt, const void* W2, int cout,
+                                            const float* bias, const float* emb, int64_t lde, const int32_t* batch_id,
+                                            const float* res, int64_t ldr, float* out, int64_t ldc, double* stats,
+                                            int64_t stats_ld, void* ws, size_t ws_bytes, void* sync, size_t sync_bytes,
+                                            int mode, int aux_ready, int cus, void* stream) {
+  if (mode < 1 || mode > 3 || cus < 0 || (cus > 0 && cus < 8)) return OFX_EINVAL;
   const int64_t ch = g2_chunk(mode);
   if (n_nodes == 0 && cin >= 1 && cout >= 1) return OFX_OK;
   if (n_nodes < 0 || cin < 1 || (cin % ch) || cout < 1 || !xp || !seg_ptr || !col || !nbr_ext || !aux || !W2 || !out ||
@@ -766,7 +766,7 @@ extern "C" int ofx_graphconv_fwd_planes(const void* xp, int64_t ldx_bytes, int c
     if (g.stats_part) used = ((size_t)ofx_cdiv(g.M, 64) * (size_t)g.N * 2 * sizeof(float) + 255) & ~(size_t)255;
     const int wm3 = (g2_wm == 2 || g2_wm == 4) ? g2_wm : g3_auto_wm(g.M, cout, a.nkt, ni);
     if (ws && used <= ws_bytes)
-      rc = ofx_launch_gconv3(a, mode, wm3, ni, (char*)ws + used, ws_bytes - used, sync, sync_bytes, st);
+      rc = ofx_launch_gconv3(a, mode, wm3, ni, (char*)ws + used, ws_bytes - used, sync, sync_bytes, st, 7, cus);
     if (rc < 0) return rc;
   }
   if (rc == 1) rc = launch((g2_wm == 2 || g2_wm == 4) ? g2_wm : wm_auto, 0, g.M);
@@ -778,6 +778,19 @@ extern "C" int ofx_graphconv_fwd_planes(const void* xp, int64_t ldx_bytes, int c
   }
   OFX_LAUNCH_CHECK();
   return OFX_OK;
+}
+
+extern "C" int ofx_graphconv_fwd_planes(const void* xp, int64_t ldx_bytes, int cin, int64_t n_nodes,
+                                        const int32_t* seg_ptr, const int32_t* col, const int32_t* nbr_ext,
+                                        const int32_t* multi_seg, int64_t n_multi, void* aux, size_t aux_bytes,
+                                        const void* tfp, int64_t ldt_bytes, int nt, const void* W2, int cout,
+                                        const float* bias, const float* emb, int64_t lde, const int32_t* batch_id,
+                                        const float* res, int64_t ldr, float* out, int64_t ldc, double* stats,
+                                        int64_t stats_ld, void* ws, size_t ws_bytes, void* sync, size_t sync_bytes,
+                                        int mode, int aux_ready, void* stream) {
+  return ofx_graphconv_fwd_planes_cus(xp, ldx_bytes, cin, n_nodes, seg_ptr, col, nbr_ext, multi_seg, n_multi, aux,
+                                      aux_bytes, tfp, ldt_bytes, nt, W2, cout, bias, emb, lde, batch_id, res, ldr, out,
+                                      ldc, stats, stats_ld, ws, ws_bytes, sync, sync_bytes, mode, aux_ready, 0, stream);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -755,7 +755,7 @@ static int g3_launch(const Gemm3Args& A, hipStream_t st) {
 }
 
 static int g3_cus_override = 0;        // > 0: plan persistent launches for at most this many compute units (ofx_set_gconv_cus)
-static int g3_cus() {                  // compute units of the current device (cached per device)
+static int g3_device_cus() {           // compute units of the current device (cached per device)
   static int cus[OFX_MAX_DEVICES] = {};
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= OFX_MAX_DEVICES) return 0;
@@ -764,8 +764,12 @@ static int g3_cus() {                  // compute units of the current device (c
     if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
     cus[dev] = n;
   }
+  return cus[dev];
+}
+static int g3_cus() {                  // ... or the process-wide override, if that is smaller
+  const int n = g3_device_cus();
   // never MORE blocks than the device can keep resident: the hand-off waits rely on it
-  return g3_cus_override > 0 && g3_cus_override < cus[dev] ? g3_cus_override : cus[dev];
+  return g3_cus_override > 0 && g3_cus_override < n ? g3_cus_override : n;
 }
 
 // Bytes of workspace the persistent launch needs behind the statistics partials (0: the shape is not eligible).
@@ -826,13 +830,20 @@ extern "C" int ofx_gconv3_plan(int64_t n_rows, int cout, int nkt, int wm, int ni
 // Called by ofx_graphconv_fwd_planes (ofx_gemm2.hip) once it has filled the common arguments.
 // Returns OFX_OK (launched), a failure status, or 1 when the shape / workspace does not qualify (caller falls back
 // to the one-tile-per-block kernel).
+// cus > 0: this launch alone is planned for that many compute units (ofx_graphconv_fwd_planes_cus), whatever
+// ofx_set_gconv_cus says -- but never for more than the device has (the hand-off waits need every block resident).
 int ofx_launch_gconv3(Gemm2Args& a, int mode, int wm, int ni, void* ws_tail, size_t ws_tail_bytes, void* sync,
-                      size_t sync_bytes, hipStream_t st, int nd) {
+                      size_t sync_bytes, hipStream_t st, int nd, int cus) {
   G3Plan p;
   GemmArgs& g = a.e;
+  if (cus > 0) {
+    const int dev_cus = g3_device_cus();
+    if (dev_cus <= 0) return 1;
+    if (cus > dev_cus) cus = dev_cus;
+  }
   if (!sync || ((uintptr_t)sync & 3) || !ws_tail || ((uintptr_t)ws_tail & 15)) return 1;
   if (!g.vec4) return 1;                   // (only the float4 epilogue exists in the persistent kernel)
-  if (!g3_plan(g.M, (int)g.N, a.nkt, wm, ni, p)) return 1;
+  if (!g3_plan(g.M, (int)g.N, a.nkt, wm, ni, p, cus)) return 1;
   if (p.part_bytes > ws_tail_bytes || (size_t)(p.G + 1) * sizeof(unsigned) > sync_bytes) return 1;
   if ((a.ldx >> 7) >= (1 << 20) || (a.ldt >> 7) >= (1 << 20) || a.n_src >= (1ll << 31)) return 1;
   Gemm3Args A = {};

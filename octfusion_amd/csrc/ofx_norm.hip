@@ -131,15 +131,18 @@ extern "C" int ofx_gn_stats_acc(const float* x, int64_t ldx, int64_t n, int C, c
   return OFX_OK;
 }
 
+// ld: channels per batch element of sums / mean / rstd (>= C: C may be a channel window of a wider tensor, whose G groups
+// are then the window's)
 __global__ void gn_finalize_kernel(const double* __restrict__ sums, const float* __restrict__ count, int B, int C, int G,
-                                   float eps, float count_eps, float* __restrict__ mean, float* __restrict__ rstd) {
+                                   int ld, float eps, float count_eps, float* __restrict__ mean,
+                                   float* __restrict__ rstd) {
   const int cpg = C / G;
   for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < B * G; t += gridDim.x * blockDim.x) {
     const int b = t / G, g = t - b * G;
     double S = 0, SS = 0;
     for (int c = g * cpg; c < (g + 1) * cpg; ++c) {
-      S += sums[((int64_t)b * C + c) * 2];
-      SS += sums[((int64_t)b * C + c) * 2 + 1];
+      S += sums[((int64_t)b * ld + c) * 2];
+      SS += sums[((int64_t)b * ld + c) * 2 + 1];
     }
     const float cnt = count[b] * (float)cpg;            // modules.py:301-302 (fp32)
     const float inv = 1.0f / (cnt + count_eps);         // reference adds eps to the COUNT (:302); nn.GroupNorm does not
@@ -148,8 +151,8 @@ __global__ void gn_finalize_kernel(const double* __restrict__ sums, const float*
     const double var = (ssd > 0 ? ssd : 0) * (double)inv;
     const float rs = (float)(1.0 / sqrt(var + (double)eps));
     for (int c = g * cpg; c < (g + 1) * cpg; ++c) {
-      mean[(int64_t)b * C + c] = (float)m;
-      rstd[(int64_t)b * C + c] = rs;
+      mean[(int64_t)b * ld + c] = (float)m;
+      rstd[(int64_t)b * ld + c] = rs;
     }
   }
 }
@@ -158,7 +161,29 @@ extern "C" int ofx_gn_finalize(const double* sums, const float* count, int batch
                                float count_eps, float* mean, float* rstd, void* stream) {
   if (!sums || !count || !mean || !rstd || batch_size < 1 || C < 1 || groups < 1 || C % groups) return OFX_EINVAL;
   gn_finalize_kernel<<<ofx_grid((int64_t)batch_size * groups, 64), 64, 0, ofx_stream(stream)>>>(
-      sums, count, batch_size, C, groups, eps, count_eps, mean, rstd);
+      sums, count, batch_size, C, groups, C, eps, count_eps, mean, rstd);
+  OFX_LAUNCH_CHECK();
+  return OFX_OK;
+}
+
+// A channel window [c_lo, c_hi) of an [n, C] tensor: whole groups, whole 32-channel chunks (ofx.h).  The windowed entry
+// points below shift every per-channel pointer by c_lo and run the ordinary launch on c_hi - c_lo channels with the
+// window's groups; only the row pitch of the statistics (GnFin::ld) stays that of the full tensor.  Per element the
+// arithmetic is that of the full launch, and nothing outside the window is read or written.
+static bool gn_window_ok(int C, int groups, int c_lo, int c_hi, int chunk = 32) {
+  if (C < 1 || groups < 1 || C % groups) return false;
+  const int cpg = C / groups;
+  return c_lo >= 0 && c_lo < c_hi && c_hi <= C && c_lo % chunk == 0 && c_hi % chunk == 0 && c_lo % cpg == 0 &&
+         c_hi % cpg == 0;
+}
+
+extern "C" int ofx_gn_finalize_window(const double* sums, const float* count, int batch_size, int C, int groups,
+                                      int c_lo, int c_hi, float eps, float count_eps, float* mean, float* rstd,
+                                      void* stream) {
+  if (!sums || !count || !mean || !rstd || batch_size < 1 || !gn_window_ok(C, groups, c_lo, c_hi)) return OFX_EINVAL;
+  const int gw = (c_hi - c_lo) / (C / groups);
+  gn_finalize_kernel<<<ofx_grid((int64_t)batch_size * gw, 64), 64, 0, ofx_stream(stream)>>>(
+      sums + 2 * (int64_t)c_lo, count, batch_size, c_hi - c_lo, gw, C, eps, count_eps, mean + c_lo, rstd + c_lo);
   OFX_LAUNCH_CHECK();
   return OFX_OK;
 }
@@ -181,13 +206,14 @@ __device__ __forceinline__ float ofx_apply_act(float v, int act) {
 constexpr int GN_APPLY_ROWS = 64;
 // (mean, rstd) of one (batch element, group) from the fp64 sums -- the arithmetic of gn_finalize_kernel, so a launch
 // that finalises on the fly (FIN) gives the same bits as ofx_gn_finalize + a launch that reads mean / rstd.
-struct GnFin { const double* sums; const float* count; int G; float eps, count_eps; };
+// ld: channels per batch element of sums AND of mean / rstd (the launch's C, or the full width when C is a window)
+struct GnFin { const double* sums; const float* count; int G; float eps, count_eps; int ld; };
 __device__ __forceinline__ void gn_group_stats(const GnFin& f, int b, int g, int C, float& mean, float& rstd) {
   const int cpg = C / f.G;
   double S = 0, SS = 0;
   for (int c = g * cpg; c < (g + 1) * cpg; ++c) {
-    S += f.sums[((int64_t)b * C + c) * 2];
-    SS += f.sums[((int64_t)b * C + c) * 2 + 1];
+    S += f.sums[((int64_t)b * f.ld + c) * 2];
+    SS += f.sums[((int64_t)b * f.ld + c) * 2 + 1];
   }
   const float cnt = f.count[b] * (float)cpg;
   const float inv = 1.0f / (cnt + f.count_eps);
@@ -318,8 +344,8 @@ __global__ void __launch_bounds__(256) gn_apply_kernel(const float* __restrict__
           rs = make_float4(rr[0], rr[1], rr[2], rr[3]);
         }
       } else {
-        m = *reinterpret_cast<const float4*>(mean + (int64_t)b * C + c);
-        rs = *reinterpret_cast<const float4*>(rstd + (int64_t)b * C + c);
+        m = *reinterpret_cast<const float4*>(mean + (int64_t)b * fin.ld + c);
+        rs = *reinterpret_cast<const float4*>(rstd + (int64_t)b * fin.ld + c);
       }
     }
     return make_float4(ofx_apply_act((v.x - m.x) * rs.x * ww.x + bb.x, act),
@@ -480,7 +506,8 @@ __global__ void __launch_bounds__(256) gn_apply_kernel(const float* __restrict__
 // mean / rstd: from ofx_gn_finalize -- or both NULL with (sums, count, groups, eps, count_eps): finalised on the fly.
 static bool gn_fin_args(const float* mean, const float* rstd, const double* sums, const float* count, int C, int groups,
                         GnFin& f) {
-  if (mean || rstd) return mean && rstd && !(((uintptr_t)mean | (uintptr_t)rstd) & 15);
+  if (f.ld < C) f.ld = C;
+  if (mean || rstd) return mean && rstd && !(((uintptr_t)mean | (uintptr_t)rstd) & 15) && f.ld % 4 == 0;
   if (!sums || !count || groups < 1 || C % groups || C > 1024) return false;
   f.sums = sums; f.count = count; f.G = groups;
   return true;
@@ -490,7 +517,7 @@ extern "C" int ofx_gn_apply(const float* x, int64_t ldx, int64_t n, int C, const
                             const float* rstd, const double* sums, const float* count, int groups, float eps,
                             float count_eps, const float* w, const float* bias, int act, float* out, int64_t ldo,
                             void* stream) {
-  GnFin f = {nullptr, nullptr, 1, eps, count_eps};
+  GnFin f = {nullptr, nullptr, 1, eps, count_eps, 0};
   if (!x || !batch_id || !w || !bias || !out || n < 0 || C < 4 || (C & 3) || C > 1024 || ldx < C ||
       ldo < C || (ldx & 3) || (ldo & 3) || ((uintptr_t)x & 15) || ((uintptr_t)out & 15) || ((uintptr_t)w & 15) ||
       ((uintptr_t)bias & 15) || act < 0 || act > 2 || !gn_fin_args(mean, rstd, sums, count, C, groups, f))
@@ -512,14 +539,15 @@ extern "C" int ofx_gn_apply(const float* x, int64_t ldx, int64_t n, int C, const
 
 extern "C" int ofx_gn_apply_rows(void) { return GN_APPLY_ROWS; }
 
-extern "C" int ofx_gn_apply_planes(const float* x, int64_t ldx, int64_t n, int C, const int32_t* batch_id,
-                                   const float* mean, const float* rstd, const double* sums, const float* count,
-                                   int groups, float eps, float count_eps, const float* w, const float* bias, int act,
-                                   int mode, void* out, int64_t ldo_bytes, const int32_t* seg_ptr, const int32_t* col,
-                                   const int32_t* multi_seg, int64_t n_multi, void* aux, const int32_t* aux_plan,
-                                   int64_t aux_left, void* stream) {
+// stats_ld: channels per batch element of mean / rstd / sums (0: C)
+static int gn_apply_planes_impl(const float* x, int64_t ldx, int64_t n, int C, const int32_t* batch_id,
+                                const float* mean, const float* rstd, const double* sums, const float* count,
+                                int groups, int stats_ld, float eps, float count_eps, const float* w, const float* bias,
+                                int act, int mode, void* out, int64_t ldo_bytes, const int32_t* seg_ptr,
+                                const int32_t* col, const int32_t* multi_seg, int64_t n_multi, void* aux,
+                                const int32_t* aux_plan, int64_t aux_left, void* stream) {
   const int chunk = g2_pairs(mode) ? 32 : 64;
-  GnFin f = {nullptr, nullptr, 1, eps, count_eps};
+  GnFin f = {nullptr, nullptr, 1, eps, count_eps, stats_ld};
   if (mode < 1 || mode > 3 || !x || !batch_id || !w || !bias || !out || n < 0 || C < chunk ||
       (C % chunk) || C > 1024 || ldx < C || (ldx & 3) || ldo_bytes < (int64_t)C * (g2_pairs(mode) ? 4 : 2) ||
       (ldo_bytes & 15) || ((uintptr_t)x & 15) || ((uintptr_t)out & 127) || ((uintptr_t)w & 15) ||
@@ -545,6 +573,37 @@ extern "C" int ofx_gn_apply_planes(const float* x, int64_t ldx, int64_t n, int C
   }
   OFX_LAUNCH_CHECK();
   return OFX_OK;
+}
+
+extern "C" int ofx_gn_apply_planes(const float* x, int64_t ldx, int64_t n, int C, const int32_t* batch_id,
+                                   const float* mean, const float* rstd, const double* sums, const float* count,
+                                   int groups, float eps, float count_eps, const float* w, const float* bias, int act,
+                                   int mode, void* out, int64_t ldo_bytes, const int32_t* seg_ptr, const int32_t* col,
+                                   const int32_t* multi_seg, int64_t n_multi, void* aux, const int32_t* aux_plan,
+                                   int64_t aux_left, void* stream) {
+  return gn_apply_planes_impl(x, ldx, n, C, batch_id, mean, rstd, sums, count, groups, 0, eps, count_eps, w, bias, act,
+                              mode, out, ldo_bytes, seg_ptr, col, multi_seg, n_multi, aux, aux_plan, aux_left, stream);
+}
+
+// Window [c_lo, c_hi) of the channels (gn_window_ok above): the plane lines of the window's chunks and the window's
+// part of every aux row are written, at the offsets they have in the full launch.
+extern "C" int ofx_gn_apply_planes_window(const float* x, int64_t ldx, int64_t n, int C, int c_lo, int c_hi,
+                                          const int32_t* batch_id, const float* mean, const float* rstd,
+                                          const double* sums, const float* count, int groups, float eps,
+                                          float count_eps, const float* w, const float* bias, int act, int mode,
+                                          void* out, int64_t ldo_bytes, const int32_t* seg_ptr, const int32_t* col,
+                                          const int32_t* multi_seg, int64_t n_multi, void* aux,
+                                          const int32_t* aux_plan, int64_t aux_left, void* stream) {
+  if (mode < 1 || mode > 3 || !x || !w || !bias || !out || C > 1024 || ldx < C ||
+      !gn_window_ok(C, groups, c_lo, c_hi, g2_pairs(mode) ? 32 : 64) ||
+      ldo_bytes < (int64_t)C * (g2_pairs(mode) ? 4 : 2))
+    return OFX_EINVAL;
+  const int64_t ob = (int64_t)c_lo * (g2_pairs(mode) ? 4 : 2);
+  return gn_apply_planes_impl(x + c_lo, ldx, n, c_hi - c_lo, batch_id, mean ? mean + c_lo : nullptr,
+                              rstd ? rstd + c_lo : nullptr, sums ? sums + 2 * (int64_t)c_lo : nullptr, count,
+                              (c_hi - c_lo) / (C / groups), C, eps, count_eps, w + c_lo, bias + c_lo, act, mode,
+                              (char*)out + ob, ldo_bytes, seg_ptr, col, multi_seg, n_multi,
+                              aux ? (char*)aux + ob : nullptr, aux_plan, aux_left, stream);
 }
 
 // ---------------------------------------------------------------------------------
@@ -710,8 +769,8 @@ __global__ void __launch_bounds__(256) gn_apply_oct_kernel(const float* __restri
         rs = make_float4(ra, (c + 1) / cpg == ga ? ra : rb2, (c + 2) / cpg == ga ? ra : rb2, rb2);
       }
     } else {
-      m = *reinterpret_cast<const float4*>(mean + (int64_t)bq * C + c);
-      rs = *reinterpret_cast<const float4*>(rstd + (int64_t)bq * C + c);
+      m = *reinterpret_cast<const float4*>(mean + (int64_t)bq * fin.ld + c);
+      rs = *reinterpret_cast<const float4*>(rstd + (int64_t)bq * fin.ld + c);
     }
   };
   auto norm = [&](int bq, const float4& q) {
@@ -786,15 +845,14 @@ __global__ void __launch_bounds__(256) gn_apply_oct_kernel(const float* __restri
   for (int p = p0 + NPRE; p < p1; ++p) entry(oct_ent[p]);
 }
 
-extern "C" int ofx_gn_apply_planes_oct(const float* x, int64_t ldx, int64_t n, int C, const int32_t* batch_id,
-                                       const float* mean, const float* rstd, const double* sums, const float* count,
-                                       int groups, float eps, float count_eps, const float* w, const float* bias, int act,
-                                       int mode, void* out, int64_t ldo_bytes, int64_t n_multi, void* aux,
-                                       const int32_t* oct_ptr, const int32_t* oct_ent, int64_t n_own, int shift,
-                                       const int32_t* left_head, const int32_t* left_src, int64_t n_left,
-                                       void* stream) {
+static int gn_apply_planes_oct_impl(const float* x, int64_t ldx, int64_t n, int C, const int32_t* batch_id,
+                                    const float* mean, const float* rstd, const double* sums, const float* count,
+                                    int groups, int stats_ld, float eps, float count_eps, const float* w,
+                                    const float* bias, int act, int mode, void* out, int64_t ldo_bytes, int64_t n_multi,
+                                    void* aux, const int32_t* oct_ptr, const int32_t* oct_ent, int64_t n_own, int shift,
+                                    const int32_t* left_head, const int32_t* left_src, int64_t n_left, void* stream) {
   const int chunk = g2_pairs(mode) ? 32 : 64;
-  GnFin f = {nullptr, nullptr, 1, eps, count_eps};
+  GnFin f = {nullptr, nullptr, 1, eps, count_eps, stats_ld};
   if (mode < 1 || mode > 3 || !x || !batch_id || !w || !bias || !out || !aux || n < 0 || C < chunk ||
       (C % chunk) || C > 1024 || ldx < C || (ldx & 3) || ldo_bytes < (int64_t)C * (g2_pairs(mode) ? 4 : 2) ||
       (ldo_bytes & 15) || ((uintptr_t)x & 15) || ((uintptr_t)out & 127) || ((uintptr_t)aux & 127) ||
@@ -823,6 +881,38 @@ extern "C" int ofx_gn_apply_planes_oct(const float* x, int64_t ldx, int64_t n, i
   }
   OFX_LAUNCH_CHECK();
   return OFX_OK;
+}
+
+extern "C" int ofx_gn_apply_planes_oct(const float* x, int64_t ldx, int64_t n, int C, const int32_t* batch_id,
+                                       const float* mean, const float* rstd, const double* sums, const float* count,
+                                       int groups, float eps, float count_eps, const float* w, const float* bias, int act,
+                                       int mode, void* out, int64_t ldo_bytes, int64_t n_multi, void* aux,
+                                       const int32_t* oct_ptr, const int32_t* oct_ent, int64_t n_own, int shift,
+                                       const int32_t* left_head, const int32_t* left_src, int64_t n_left,
+                                       void* stream) {
+  return gn_apply_planes_oct_impl(x, ldx, n, C, batch_id, mean, rstd, sums, count, groups, 0, eps, count_eps, w, bias,
+                                  act, mode, out, ldo_bytes, n_multi, aux, oct_ptr, oct_ent, n_own, shift, left_head,
+                                  left_src, n_left, stream);
+}
+
+extern "C" int ofx_gn_apply_planes_oct_window(const float* x, int64_t ldx, int64_t n, int C, int c_lo, int c_hi,
+                                              const int32_t* batch_id, const float* mean, const float* rstd,
+                                              const double* sums, const float* count, int groups, float eps,
+                                              float count_eps, const float* w, const float* bias, int act, int mode,
+                                              void* out, int64_t ldo_bytes, int64_t n_multi, void* aux,
+                                              const int32_t* oct_ptr, const int32_t* oct_ent, int64_t n_own, int shift,
+                                              const int32_t* left_head, const int32_t* left_src, int64_t n_left,
+                                              void* stream) {
+  if (mode < 1 || mode > 3 || !x || !w || !bias || !out || !aux || C > 1024 || ldx < C ||
+      !gn_window_ok(C, groups, c_lo, c_hi, g2_pairs(mode) ? 32 : 64) ||
+      ldo_bytes < (int64_t)C * (g2_pairs(mode) ? 4 : 2))
+    return OFX_EINVAL;
+  const int64_t ob = (int64_t)c_lo * (g2_pairs(mode) ? 4 : 2);
+  return gn_apply_planes_oct_impl(x + c_lo, ldx, n, c_hi - c_lo, batch_id, mean ? mean + c_lo : nullptr,
+                                  rstd ? rstd + c_lo : nullptr, sums ? sums + 2 * (int64_t)c_lo : nullptr, count,
+                                  (c_hi - c_lo) / (C / groups), C, eps, count_eps, w + c_lo, bias + c_lo, act, mode,
+                                  (char*)out + ob, ldo_bytes, n_multi, (char*)aux + ob, oct_ptr, oct_ent, n_own, shift,
+                                  left_head, left_src, n_left, stream);
 }
 
 // elementwise activation (shared with ofx_misc entry point)

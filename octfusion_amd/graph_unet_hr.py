@@ -14,7 +14,7 @@ import torch.nn as nn
 
 from . import ops
 from .modules import (GraphConv, GraphDownsample, GraphResBlockEmbed, GraphUpsample, _Linear,
-                      graphnormalization)
+                      graphnormalization, skip_window)
 
 
 def level_plan(input_depth, channel_mult, num_res_blocks):
@@ -219,6 +219,27 @@ class UNet3DModel(nn.Module):
             c_mid = self.middle_block1.out_channels
             mid = torch.empty(n_at[d], 2 * c_mid, dtype=torch.float32, device=dev)
             h = self.middle_block1(h, emb, doctree, d, emb_act=emb_act, out=mid[:, :c_mid], emb_out=emb_outs[id(self.middle_block1)])
+            # skip-ahead (ops.SKIP_AHEAD): every skip tensor, its statistics and the decoder's
+            # weights are known from here on, and the nested net that follows is a chain of small launches that leaves
+            # most of the chip idle -- the skip half of the decoder blocks' conv1 runs beside it on a second stream,
+            # planned for a subset of the compute units.  Joined BEFORE middle_block2: its convolutions are planned for
+            # the whole chip again, and two persistent launches must fit on the device together.
+            # A nested SPARSE net (the feature stage nests this class) is no such shadow: its own convolutions are
+            # persistent launches planned for the whole chip.  Nor is there room while sampler lanes share the chip.
+            ahead_ok = ops.SKIP_AHEAD and not ops.LANE_CUS and not isinstance(unet_lr, UNet3DModel)
+            ahead_main, ahead_side = ops.skip_ahead_stream(dev) if ahead_ok else (None, None)
+            if ahead_side is not None:
+                todo, si = [], len(hs)
+                for (kind, dd, _), module in zip(self._dec, self.output_blocks):
+                    if kind == 'res':
+                        si -= 1
+                        win = skip_window(self._cat_plan[si][0], self._cat_plan[si][1], module.block1_norm.group)
+                        if win is not None:
+                            todo.append((n_at[dd] * (win[1] - win[0]) * module.out_channels, si, dd, module))
+                with torch.cuda.stream(ahead_side):
+                    for _, si, dd, module in sorted(todo, key=lambda t_: -t_[0]):       # largest first
+                        module.prepare_skip(cat_bufs[si], doctree, dd, ops.SKIP_AHEAD_CUS, c_h=self._cat_plan[si][0],
+                                            skip_stats=ops.get_stats(hs[si]))
             if 'out' in inspect.signature(unet_lr.forward_as_middle).parameters:
                 h_lr = unet_lr.forward_as_middle(h, doctree, timesteps, label, context, out=mid[:, c_mid:])
             else:
@@ -227,7 +248,12 @@ class UNet3DModel(nn.Module):
                 h = ops.cat_channels(h, h_lr, buf=mid)
             else:
                 h = ops.cat_channels(h, h_lr)
-            h = self.middle_block2(h, emb, doctree, d, emb_act=emb_act, emb_out=emb_outs[id(self.middle_block2)])
+            if ahead_side is not None:
+                ahead_main.wait_stream(ahead_side)
+            # (straight into the left columns of the first decoder concat: no copy)
+            last = len(cat_bufs) - 1
+            h = self.middle_block2(h, emb, doctree, d, emb_act=emb_act, emb_out=emb_outs[id(self.middle_block2)],
+                                   out=cat_bufs[last][:, :self._cat_plan[last][0]])
 
         # decoder: block j consumes skip len(hs)-1-j; its own output goes to the left columns of the NEXT
         # consumer's buffer when the next module is a res block
@@ -250,7 +276,10 @@ class UNet3DModel(nn.Module):
                     if st is not None:
                         setattr(left, ops.STATS_ATTR, st)
                     pending = left
-                hcat = ops.cat_channels(pending, hs[si], buf=cat_bufs[si])
+                if module.ahead_pending(cat_bufs[si], h_stats=ops.get_stats(pending)):
+                    hcat = cat_bufs[si]                             # (the block completes the statistics itself)
+                else:
+                    hcat = ops.cat_channels(pending, hs[si], buf=cat_bufs[si])
                 pending = module(hcat, emb, doctree, dd, emb_act=emb_act, out=out_slot, emb_out=emb_outs[id(module)])
                 j += 1
             else:

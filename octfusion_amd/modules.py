@@ -416,6 +416,21 @@ class TimestepBlock(nn.Module):
     pass
 
 
+def skip_window(c_h, c_skip, groups):
+    """Channel window (c_lo, c_hi) of a decoder concat [h (c_h) | skip (c_skip)], normalised in `groups` groups, whose
+    GroupNorm + conv1 contribution needs the skip half alone: c_hi = c_h + c_skip, c_lo = the smallest multiple of
+    lcm(channels per group, 32) that is >= c_h (whole groups: no statistics of h; whole 32-channel chunks: whole plane
+    lines and k-steps).  None if fewer than 32 channels remain."""
+    C = c_h + c_skip
+    if groups < 1 or C % groups:
+        return None
+    step = math.lcm(C // groups, 32)
+    c_lo = (c_h + step - 1) // step * step
+    if C % 32 or C - c_lo < 32:
+        return None
+    return c_lo, C
+
+
 class GraphResBlockEmbed(TimestepBlock):
     """reference modules.py:661-763.  use_scale_shift_norm must stay False (the reference
     branch reads a non-existent attribute, :747-751)."""
@@ -443,12 +458,120 @@ class GraphResBlockEmbed(TimestepBlock):
             self.skip_connection = nn.Identity()
         else:
             self.skip_connection = Conv1x1(self.channels, self.out_channels)
+        self._pw2_win = {}             # (early | late, mode, window) -> (parameter key, PackedPlanes)
+        self._ahead = None             # what prepare_skip() left for the next forward()
+
+    def _window_pack(self, part, mode, window):
+        """conv1's weights restricted to the K window (part 'early': rows [c_lo, c_hi) of every direction, no node-type
+        rows) or to its complement (part 'late': rows [0, c_lo) + the node-type rows), in the planes pack; cached per
+        (parameter version, mode, window) like GraphConv._pw2."""
+        conv = self.conv1
+        w = conv.weights
+        nt = conv.n_node_type if conv.n_node_type > 1 else 0
+        key = (w.data_ptr(), w._version, tuple(w.shape))
+        hit = self._pw2_win.get((part, mode, window))
+        if hit is not None and hit[0] == key:
+            return hit[1]
+        c_lo, c_hi = window
+        w3 = w.detach().view(7, conv.in_channels + nt, conv.out_channels)
+        if part == 'early':
+            ww, cin_w, nt_w = w3[:, c_lo:c_hi], c_hi - c_lo, 0
+        else:
+            ww, cin_w, nt_w = torch.cat([w3[:, :c_lo], w3[:, conv.in_channels:]], dim=1), c_lo, conv.n_node_type
+        ww = ww.contiguous().view(-1, conv.out_channels)
+        pw = ops.PackedPlanes().get(ww, cin_w, nt_w, mode)
+        self._pw2_win[(part, mode, window)] = (key, pw)
+        return pw
+
+    @torch.no_grad()
+    def prepare_skip(self, x_cat, doctree, depth, cus=0, c_h=None, skip_stats=None):
+        """The skip half of conv1(SiLU(GN(cat[h, skip]))), ahead of time: ``x_cat`` is the [N, c_h + c_skip] concat
+        buffer of which only the skip columns [c_h, C) are written yet, ``skip_stats`` their fp64 GroupNorm sums
+        [B, c_skip, 2].  Normalises the window skip_window() allows into this block's planes buffer (+ the window's
+        part of the aux rows) and contracts it with the window's weight rows into a partial [N, Cout], the persistent
+        launch planned for ``cus`` compute units.  The next forward() on the same buffer finishes the block from
+        there.  Returns False (nothing launched) when the block does not qualify."""
+        self._ahead = None
+        conv, norm = self.conv1, self.block1_norm
+        C = self.channels
+        mode = conv.planes_mode(doctree, depth)
+        win = skip_window(c_h, C - c_h, norm.group) if c_h is not None and 0 < c_h < C else None
+        if (win is None or skip_stats is None or not ops.planes_pairs(mode) or x_cat.shape[1] != C
+                or (win[1] - win[0]) < ops.SKIP_AHEAD_MIN_SHARE * C):
+            return False
+        n, dev, B = x_cat.shape[0], x_cat.device, doctree.batch_size
+        seg_ptr, col, _, _ = doctree.csr(depth)
+        _, multi_seg, n_multi = doctree.ext(depth)
+        oct_plan = doctree.oct_plan(depth) if ops.AUX_PLAN == 'oct' else None
+        block_plan = doctree.aux_plan(depth) if ops.AUX_PLAN and oct_plan is None else None
+        g = ops.AuxGraph(seg_ptr, col, multi_seg, n_multi, oct_plan, block_plan)
+        hp = torch.empty(n, C, dtype=torch.float32, device=dev)
+        if not ops.planes_ok(hp, mode):
+            return False
+        # (one row of slack: the windowed convolution hands the kernel aux + c_lo * 4 bytes with the full row pitch)
+        aux = torch.empty((n_multi + 2) * C * 4, dtype=torch.uint8, device=dev)
+        sums = torch.empty(B, C, 2, dtype=torch.float64, device=dev)
+        sums[:, c_h:].copy_(skip_stats.view(B, C - c_h, 2))
+        mean = rstd = None
+        if ops._gn_launch(mode, g, n * C, C // norm.group)[1]:
+            mean = torch.empty(B * C, dtype=torch.float32, device=dev)
+            rstd = torch.empty(B * C, dtype=torch.float32, device=dev)
+        ops.group_norm_window(x_cat, doctree.batch_id32(depth), doctree.count(depth), B, norm.weights, norm.bias,
+                              norm.group, win, sums.view(-1), hp, aux, mode, g, norm.eps, 'silu', mean, rstd)
+        part = ops.graphconv_planes(hp, mode, seg_ptr, col, doctree.ext(depth), self._window_pack('early', mode, win),
+                                    win[1] - win[0], 0, window=win, cus=cus)
+        self._ahead = dict(buf=x_cat.data_ptr(), c_h=c_h, win=win, mode=mode, g=g, hp=hp, aux=aux, sums=sums, mean=mean,
+                           rstd=rstd, part=part, depth=depth)
+        return True
+
+    def ahead_pending(self, x_cat, h_stats=None):
+        """True if prepare_skip() ran for this concat buffer and the next forward() on it will finish from the partial;
+        ``h_stats``: the GroupNorm sums [B, c_h, 2] of the h columns, if their producer attached them."""
+        a = self._ahead
+        if a is None or a['buf'] != x_cat.data_ptr():
+            return False
+        a['h_stats'] = h_stats
+        return True
+
+    def _finish_ahead(self, x, doctree, depth, emb_out):
+        """conv1(SiLU(GN(x))) from what prepare_skip() left: the statistics of the h columns complete the sums, the
+        channels [0, c_lo) are normalised into the same planes / aux buffers and contracted (+ the node-type rows, the
+        embedding and the statistics epilogue) on top of the partial."""
+        a, self._ahead = self._ahead, None
+        conv, norm = self.conv1, self.block1_norm
+        c_h, (c_lo, c_hi), mode, B = a['c_h'], a['win'], a['mode'], doctree.batch_size
+        bid = doctree.batch_id32(depth)
+        st, st_c = a.get('h_stats'), c_h                     # sums of the h columns alone (ahead_pending(h_stats=)) ...
+        if st is None:
+            st, st_c = ops.get_stats(x), self.channels       # ... or of the whole concat, or none yet
+        if st is not None:
+            a['sums'][:, :c_h].copy_(st.view(B, st_c, 2)[:, :c_h])
+        else:
+            a['sums'][:, :c_h].copy_(ops.gn_sums(x[:, :c_h], bid, B).view(B, c_h, 2))
+        hp = ops.group_norm_window(x, bid, doctree.count(depth), B, norm.weights, norm.bias, norm.group, (0, c_lo),
+                                   a['sums'].view(-1), a['hp'], a['aux'], mode, a['g'], norm.eps, 'silu', a['mean'],
+                                   a['rstd'])
+        nt = conv.n_node_type if conv.n_node_type > 1 else 0
+        seg_ptr, col, N, _ = doctree.csr(depth)
+        stats = None
+        if conv.emit_stats and N * conv.out_channels >= (1 << 14) and conv.out_channels % 4 == 0:
+            stats = ops.stats_zeros(B * conv.out_channels * 2, x.device)
+        y = ops.graphconv_planes(hp, mode, seg_ptr, col, doctree.ext(depth), self._window_pack('late', mode, a['win']),
+                                 c_lo, nt, doctree.type_frac_planes(depth, nt, mode) if nt else None,
+                                 conv.bias if conv.use_bias else None, emb_out, bid,
+                                 a['part'], None, stats=stats, window=(0, c_lo))
+        if stats is not None:
+            setattr(y, ops.STATS_ATTR, stats)
+        return y
 
     @torch.no_grad()
     def forward(self, x, emb, doctree, depth, emb_act=None, out=None, emb_out=None):
         """``emb_act``: optional precomputed SiLU(emb) shared by all blocks of a step; ``emb_out``: optional
         precomputed emb_layers(emb) [B, Cout] (the U-Net evaluates the emb_layers of ALL its blocks in one GEMM);
         ``out``: optional destination (may be a column slice of a wider buffer: zero-copy skip concatenation)."""
+        ahead = self._ahead
+        if ahead is not None and (ahead['buf'] != x.data_ptr() or ahead['depth'] != depth or x.shape[1] != self.channels):
+            ahead = self._ahead = None         # (prepared for another tensor: dropped)
         skip, side = x, None
         if not isinstance(self.skip_connection, nn.Identity):
             if ops.SIDE_STREAM:
@@ -460,13 +583,16 @@ class GraphResBlockEmbed(TimestepBlock):
                     skip = self.skip_connection(x)
             else:
                 skip = self.skip_connection(x)
-        h = self.block1_norm(x, doctree, depth, act='silu', planes=self.conv1.planes_mode(doctree, depth))
         if emb_out is None:
             if emb_act is None:
                 emb_act = ops.act(emb, 'silu')
             emb_out = self.emb_layers[1](emb_act)                   # [B, Cout]
         assert doctree.batch_size == emb_out.shape[0]
-        h = self.conv1(h, doctree, depth, emb=emb_out)              # + emb_out[batch_id] fused
+        if ahead is not None:
+            h = self._finish_ahead(x, doctree, depth, emb_out)
+        else:
+            h = self.block1_norm(x, doctree, depth, act='silu', planes=self.conv1.planes_mode(doctree, depth))
+            h = self.conv1(h, doctree, depth, emb=emb_out)          # + emb_out[batch_id] fused
         h = self.block2_norm(h, doctree, depth, act='silu', out=h, planes=self.conv2.planes_mode(doctree, depth))
         if side is not None:
             main.wait_stream(side)

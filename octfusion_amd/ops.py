@@ -283,19 +283,32 @@ class PackedPlanes:
 
 
 def graphconv_planes(xp, mode, seg_ptr, col, ext, pw, cin, nt, tf_planes=None, bias=None, emb=None, batch_id=None,
-                     res=None, out=None, stats=None):
-    """Fused GraphConv on operand planes (ofx_graphconv_fwd_planes)."""
-    assert planes_of(xp) == mode and xp.shape[1] == cin
+                     res=None, out=None, stats=None, window=None, cus=0):
+    """Fused GraphConv on operand planes (ofx_graphconv_fwd_planes).
+    window (c_lo, c_hi): contract over that channel window of xp only (cin = c_hi - c_lo, whole 32-channel chunks; pw
+    packed from the window's weight rows): the kernel gets the window's first plane line of every row and aux row and
+    the full row pitch.  xp must carry its aux rows, with c_lo * 4 bytes of slack behind the last one.
+    cus > 0: plan the persistent launch for that many compute units (ofx_graphconv_fwd_planes_cus)."""
+    assert planes_of(xp) == mode
     N = xp.shape[0]
     bpc = 4 if planes_pairs(mode) else 2
-    ldx = xp.stride(0) * bpc if N > 1 else cin * bpc
+    ldx = xp.stride(0) * bpc if N > 1 else xp.shape[1] * bpc
+    c_lo = 0
+    if window is not None:
+        c_lo, c_hi = window
+        assert planes_pairs(mode) and c_lo % 32 == 0 and c_hi % 32 == 0 and 0 <= c_lo < c_hi <= xp.shape[1]
+        assert cin == c_hi - c_lo
+    else:
+        assert xp.shape[1] == cin
+    off = c_lo * bpc
     out, ldc = _out2d(out, N, pw.N, xp.device)
     nbr_ext, multi_seg, n_multi = ext
     aux = getattr(xp, AUX_ATTR, None)           # written by the producer of xp (group_norm(..., aux_graph=))
     aux_ready = 1 if aux is not None else 0
     if aux is None:
+        assert window is None
         aux = torch.empty((n_multi + 1) * ldx, dtype=torch.uint8, device=xp.device)
-    assert aux.numel() >= (n_multi + 1) * ldx
+    assert aux.numel() - off >= (n_multi + 1) * ldx
     emb, lde = _row_major(emb)
     if emb is not None or stats is not None:
         _chk(batch_id, torch.int32)
@@ -311,11 +324,39 @@ def graphconv_planes(xp, mode, seg_ptr, col, ext, pw, cin, nt, tf_planes=None, b
         sync = sync_words(xp.device)
         _meta('graphconv', flops, 0, (N, pw.cin, pw.N, 'planes', 'emb' if emb is not None else '',
                                       'res' if res is not None else '', 'stats' if stats is not None else ''))
-        call('ofx_graphconv_fwd_planes', ptr(xp), ldx, cin, N, ptr(seg_ptr), ptr(col), ptr(nbr_ext), ptr(multi_seg),
-             n_multi, ptr(aux), aux.numel() * aux.element_size(), ptr(tf_planes), ldt, nt, ptr(pw.t), pw.N, ptr(bias),
-             ptr(emb), lde, ptr(batch_id) if (emb is not None or stats is not None) else None, ptr(res), ldr, ptr(out),
-             ldc, ptr(stats), pw.N, ptr(ws), ws.numel(), ptr(sync), sync.numel() * 4, mode, aux_ready, stream())
+        args = (ptr(xp) + off, ldx, cin, N, ptr(seg_ptr), ptr(col), ptr(nbr_ext), ptr(multi_seg), n_multi, ptr(aux) + off,
+                aux.numel() * aux.element_size() - off, ptr(tf_planes), ldt, nt, ptr(pw.t), pw.N, ptr(bias), ptr(emb), lde,
+                ptr(batch_id) if (emb is not None or stats is not None) else None, ptr(res), ldr, ptr(out), ldc,
+                ptr(stats), pw.N, ptr(ws), ws.numel(), ptr(sync), sync.numel() * 4, mode, aux_ready)
+        if cus:
+            call('ofx_graphconv_fwd_planes_cus', *args, int(cus), stream())
+        else:
+            call('ofx_graphconv_fwd_planes', *args, stream())
     return out
+
+
+# Skip-ahead: the skip half of a decoder res block's conv1(SiLU(GN(cat[h, skip]))) depends on the
+# encoder alone, so the hr net runs it on a second stream, planned for SKIP_AHEAD_CUS compute units, while the nested
+# dense net's chain of small launches leaves most of the chip idle.  OFX_SKIP_AHEAD=0: the one-launch path.
+# SKIP_AHEAD_MIN_SHARE: the eligibility rule -- only blocks whose window holds at least this share of the concat's
+# channels are split.
+SKIP_AHEAD = os.environ.get('OFX_SKIP_AHEAD', '1') == '1'
+SKIP_AHEAD_CUS = int(os.environ.get('OFX_SKIP_AHEAD_CUS', '128'))
+SKIP_AHEAD_MIN_SHARE = float(os.environ.get('OFX_SKIP_AHEAD_MIN_SHARE', '0'))
+
+
+def skip_ahead_stream(device):
+    """(main, side) for the skip-ahead branch of a step, or (None, None) off a HIP device / when the current stream IS
+    the side stream.  The side stream waits for everything issued on main so far; the caller joins with
+    main.wait_stream(side) before the first result is read (the allocator invariant of fork_stream holds likewise)."""
+    if device.type != 'cuda':
+        return None, None
+    s = _scratch('skip_ahead', device, False, lambda: torch.cuda.Stream(device))
+    main = torch.cuda.current_stream(device)
+    if main.cuda_stream == s.cuda_stream:
+        return None, None
+    s.wait_stream(main)
+    return main, s
 
 
 # OFX_SIDE_STREAM=1: run the 1x1 skip convolutions of the res-blocks on a second stream, concurrently with the conv1
@@ -324,10 +365,15 @@ def graphconv_planes(xp, mode, seg_ptr, col, ext, pw, cin, nt, tf_planes=None, b
 SIDE_STREAM = os.environ.get('OFX_SIDE_STREAM', '0') == '1'
 
 
+LANE_CUS = 0        # what set_lane_cus() last set: while lanes share the chip, nothing else is planned beside them (SKIP_AHEAD)
+
+
 def set_lane_cus(cus):
     """Compute units a persistent GraphConv launch is planned for while sampler.sample_loop runs a stage as lanes
     (ofx_set_gconv_cus, include/ofx.h); 0 = the whole device."""
+    global LANE_CUS
     call('ofx_set_gconv_cus', int(cus))
+    LANE_CUS = int(cus)
 
 
 def side_stream(device):
@@ -1149,6 +1195,64 @@ def group_norm(x, batch_id, count, batch_size, weight, bias, groups, eps=1e-5, a
     _meta('gn_apply', 0, 8.0 * n * C, (n, C, 'fp32'))
     call('ofx_gn_apply', ptr(x), ldx, n, C, ptr(batch_id), ptr(mean), ptr(rstd), ptr(sums), ptr(count), groups, eps, count_eps,
          ptr(w), ptr(b), ACT[act], ptr(out), ldo, stream())
+    return out
+
+
+def gn_sums(x, batch_id, batch_size):
+    """fp64 GroupNorm sums [B * C * 2] of x [n, C] (a column slice of a wider buffer is fine)."""
+    x, ldx = _row_major(x)
+    n, C = x.shape
+    sums = torch.empty(batch_size * C * 2, dtype=torch.float64, device=x.device)
+    _meta('gn_stats', 0, 4.0 * n * C, (n, C))
+    call('ofx_gn_stats', ptr(x), ldx, n, C, ptr(batch_id), batch_size, ptr(sums), stream())
+    return sums
+
+
+def group_norm_window(x, batch_id, count, batch_size, weight, bias, groups, window, sums, out, aux, planes, aux_graph,
+                      eps=1e-5, act=None, mean=None, rstd=None, count_eps=None):
+    """The planes branch of group_norm() on the channel window (c_lo, c_hi) of x [n, C] (ofx.h, "channel windows"):
+    the window's plane lines of `out` ([n, C] fp32-shaped, pair planes) and the window's part of the aux rows in `aux`
+    (uint8, pitch = the row pitch of out).  sums: fp64 [B, C, 2] of the FULL tensor, of which only the window's groups
+    need to be final.  mean / rstd: [B * C] buffers when the launch kind of the full tensor (_gn_launch) takes the
+    finalize launch -- the windows of one tensor share them.  Calls on complementary windows leave the bytes of one
+    full group_norm(..., planes=, aux_graph=)."""
+    if count_eps is None:
+        count_eps = eps
+    x, ldx = _row_major(x)
+    n, C = x.shape
+    c_lo, c_hi = window
+    assert planes_pairs(planes) and aux_graph is not None and out.shape == (n, C) and out.data_ptr() != x.data_ptr()
+    _chk(sums, torch.float64)
+    assert sums.numel() == batch_size * C * 2
+    range_words(x.device)
+    w = weight.detach().reshape(-1)
+    b = bias.detach().reshape(-1)
+    launch, finalize = _gn_launch(planes, aux_graph, n * C, C // groups)
+    if finalize:
+        assert mean is not None and rstd is not None and mean.numel() == batch_size * C == rstd.numel()
+        _meta('gn_finalize', 0, 24.0 * batch_size * (c_hi - c_lo), (batch_size, c_hi - c_lo))
+        call('ofx_gn_finalize_window', ptr(sums), ptr(count), batch_size, C, groups, c_lo, c_hi, eps, count_eps,
+             ptr(mean), ptr(rstd), stream())
+    else:
+        mean = rstd = None
+    out, ldo = _planes_out(n, C, planes, x.device, out)
+    seg_ptr, col, multi_seg, n_multi = aux_graph[:4]
+    assert aux.numel() >= (n_multi + 1) * ldo
+    _meta('gn_apply', 0, (8.0 * n + 4.0 * (n_multi + 1)) * (c_hi - c_lo), (n, c_hi - c_lo, 'planes+aux window'))
+    if launch == 'oct':
+        op, shift, n_own, n_left, (o_ptr, o_ent, o_head, o_src) = aux_graph.oct_plan
+        base = op.data_ptr()
+        call('ofx_gn_apply_planes_oct_window', ptr(x), ldx, n, C, c_lo, c_hi, ptr(batch_id), ptr(mean), ptr(rstd),
+             ptr(sums), ptr(count), groups, eps, count_eps, ptr(w), ptr(b), ACT[act], planes, ptr(out), ldo, n_multi,
+             ptr(aux), base + 4 * o_ptr, base + 4 * o_ent, n_own, shift, base + 4 * o_head, base + 4 * o_src, n_left,
+             stream())
+    else:
+        plan, n_left = aux_graph.block_plan if launch == 'block' else (None, 0)
+        call('ofx_gn_apply_planes_window', ptr(x), ldx, n, C, c_lo, c_hi, ptr(batch_id), ptr(mean), ptr(rstd), ptr(sums),
+             ptr(count), groups, eps, count_eps, ptr(w), ptr(b), ACT[act], planes, ptr(out), ldo, ptr(seg_ptr), ptr(col),
+             ptr(multi_seg), n_multi, ptr(aux), ptr(plan), n_left, stream())
+    setattr(out, AUX_ATTR, aux)
+    setattr(out, PLANES_ATTR, planes)
     return out
 
 
