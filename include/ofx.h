@@ -944,6 +944,52 @@ int ofx_mesh_sdf(const float* verts, const int32_t* faces, const int64_t* vert_o
  * bins), words[2] += triangles evaluated after the per-triangle box test (x 64 = point-triangle pairs).  Sticky. */
 int ofx_mesh_sdf_set_counters(unsigned long long* words);
 
+/* ------------------------------------------------------------------ rendering (csrc/ofx_render.hip)
+ * Shaded views of triangle meshes for the reference's FID image sets (utils/render_utils.py:14-23, utils/render/):
+ * a deterministic renderer of the project's own, parity with pyrender unpinned; tests/render_oracle.py
+ * restates every stage.  `batch` meshes concatenated as for ofx_surface_sample: verts [V, 3] fp32, faces [F, 3] int32,
+ * 0-based into the shape's own vertices (the caller checks them); offs (int64 device) = [vert_off[batch],
+ * vert_cnt[batch], face_off[batch], face_cnt[batch]]; max_verts / max_faces = the largest count of one shape.
+ * cam [views, 24] fp64 (device): per view the view matrix (world -> camera) and then the pose (camera -> world), each
+ * the top 3 x 4 rows, row-major; the pose is rigid.  The camera looks down -z, y up, aspect 1, tan_half_fov =
+ * tan(yfov / 2); image row 0 is the top.  Every float64 operation is individually rounded, in the oracle's order.
+ * ofx_render_project: norm [batch, 4] fp64 = (centre, scale) per shape: with normalize the centre of the bounding box
+ *   and the largest distance of a vertex from it (min / max reductions only; non-finite vertices are left out; a shape
+ *   without extent gets scale 1), else (0, 0, 0, 1).  Per (view, vertex), p = (v - centre) / scale, e = view * p,
+ *   w = -e.z, f = 1 / tan_half_fov: sxy [views, V, 2] int32 = rint(((e.x f) / w + 1) * 128 size), rint((1 - (e.y f)
+ *   / w) * 128 size) -- screen position in 1/256 pixel, pixel (i, j) has its centre at (256 i + 128, 256 j + 128);
+ *   depth [views, V] fp64 = window depth ((zfar + znear) / (zfar - znear) + 1) / 2 - (zfar znear / (zfar - znear)) / w,
+ *   affine in screen space.  A vertex with w < znear, a non-finite coordinate or a screen coordinate beyond +-2^26
+ *   units (all written so that a NaN fails) gets sxy = (INT32_MIN, 0), depth 0: its triangles are dropped.
+ * ofx_render_raster: keys [batch, views, size, size] uint64 = min over the triangles covering the pixel centre of
+ *   (floor(depth * 2^32) clamped to [0, 2^32 - 1]) << 32 | face index; all ones where nothing covers.  A triangle with
+ *   a dropped vertex covers nothing and adds 1 to dropped [batch, views] int32.  The vertices are ordered so that
+ *   area2 = (b - a) x (c - a) > 0 (b and c swapped otherwise: both windings are drawn; area2 == 0 covers nothing).
+ *   With E_ab(p) = (b.x - a.x)(p.y - a.y) - (b.y - a.y)(p.x - a.x) in int64, p is covered iff for each edge E > 0, or
+ *   E == 0 and the edge is a left edge (b.y < a.y) or a top edge (b.y == a.y, b.x > a.x).  depth(p) = ((E_bc z_a +
+ *   E_ca z_b) + E_ab z_c) / area2.  Resolution is a 64-bit atomic minimum: the result does not depend on order, and
+ *   on equal quantised depth the lowest face index wins.  A triangle whose pixel box, clamped to the screen, holds
+ *   more than big_px pixels goes to a list (ws: ofx_render_raster_ws_bytes) and is rasterised by a wave, the others
+ *   by a thread: the keys do not depend on big_px.
+ * ofx_render_shade: image [batch, views, size, size, 3] uint8 = floor(255 clamp(c, 0, 1) + 0.5); c is the background
+ *   where the key is all ones, else the flat two-sided glTF 2.0 metallic-roughness shading of the key's triangle under
+ *   a directional, a point and a spot light at the camera (DESIGN.md 4.14 has the closed form).  params (host, 13
+ *   fp64): base colour rgb, metallic, roughness, directional / point / spot intensity, spot angle scale and offset,
+ *   background rgb.
+ * Bad arguments: OFX_EINVAL, nothing launched.  Limits: batch * views <= 65535, size <= OFX_RENDER_MAX_SIZE,
+ * V and F < 2^31. */
+#define OFX_RENDER_MAX_SIZE 4096
+int ofx_render_project(const float* verts, const int64_t* offs, int batch, int64_t total_verts, int64_t max_verts,
+                       const double* cam, int views, int size, double tan_half_fov, double znear, double zfar,
+                       int normalize, double* norm, int32_t* sxy, double* depth, void* stream);
+size_t ofx_render_raster_ws_bytes(int views, int64_t total_faces);
+int ofx_render_raster(const int32_t* faces, const int64_t* offs, int batch, int64_t total_verts, int64_t total_faces,
+                      int64_t max_faces, int views, int size, const int32_t* sxy, const double* depth, int64_t big_px,
+                      uint64_t* keys, int32_t* dropped, void* ws, void* stream);
+int ofx_render_shade(const float* verts, const int32_t* faces, const int64_t* offs, int batch, const double* norm,
+                     const double* cam, int views, int size, double tan_half_fov, const uint64_t* keys,
+                     const double* params, uint8_t* image, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,7 @@ c_p = ctypes.c_void_p
 c_i = ctypes.c_int
 c_l = ctypes.c_int64
 c_f = ctypes.c_float
+c_d = ctypes.c_double
 c_sz = ctypes.c_size_t
 c_u64 = ctypes.c_uint64
 
@@ -196,6 +197,10 @@ _SIGS = {
     'ofx_mesh_sdf_ws_bytes': (c_sz, [c_i, c_l, c_l, c_i], False),
     'ofx_mesh_sdf': (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p], True),
     'ofx_mesh_sdf_set_counters': (c_i, [c_p], True),
+    'ofx_render_project': (c_i, [c_p, c_p, c_i, c_l, c_l, c_p, c_i, c_i, c_d, c_d, c_d, c_i, c_p, c_p, c_p, c_p], True),
+    'ofx_render_raster_ws_bytes': (c_sz, [c_i, c_l], False),
+    'ofx_render_raster': (c_i, [c_p, c_p, c_i, c_l, c_l, c_l, c_i, c_i, c_p, c_p, c_l, c_p, c_p, c_p, c_p], True),
+    'ofx_render_shade': (c_i, [c_p, c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_d, c_p, ctypes.POINTER(c_d), c_p, c_p], True),
 }
 
 EXPORTS = sorted(_SIGS)

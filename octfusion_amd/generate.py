@@ -18,6 +18,7 @@ mesh.py lists the differences).
     python -m octfusion_amd.generate --config snet_uncond --shapes 8 --mesh --out samples     # + samples/<i>.obj
     python -m octfusion_amd.generate --config snet_uncond --shapes 8 --mesh --points 2048 --out samples  # + <i>.npy
     python -m octfusion_amd.generate --config snet_uncond --shapes 8 --mesh --clean --out samples   # largest component
+    python -m octfusion_amd.generate --config snet_uncond --shapes 8 --mesh --views --out samples   # + fid_images/
     python -m octfusion_amd.generate --config snet_uncond --shapes 8 --no-vae --octree-mesh --out samples
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \\
         -m octfusion_amd.generate --config snet_cond --shapes 32 --category 2
@@ -80,16 +81,21 @@ def prepare(config, rank, device, ckpt=None, vae_ckpt=None, with_vae=True, allow
 
 def generate(net, cfg, n_shapes, rank, world, seed=0, ddim_steps=200, label=None, vae=None, out_dir=None,
              shapes_per_call=1, use_graph=None, sdf_resolution=None, timings=None, mesh=False, mesh_level=0.0,
-             mesh_scale=1.0, points=None, mesh_clean=False, octree_mesh=False):
+             mesh_scale=1.0, points=None, mesh_clean=False, octree_mesh=False, views=False, view_size=299):
     """Yields (result indices, output dict, seconds) for every group of shapes this rank owns.  mesh: also
     out['meshes'] (needs the VAE and sdf_resolution), written as <out_dir>/<index>.obj.  points (needs mesh): also
     out['points'] = {position in the group: [points, 3] cloud} of every non-empty mesh, sampled on the device after the
     unit-cube normalisation (metrics.sample_surface keyed by the result index), written as <out_dir>/<index>.npy.
     mesh_clean (needs mesh): the meshes, files and clouds are those of each shape's largest component, and
     out['mesh_components'] holds the component counts before cleaning.  octree_mesh: also out['octree_meshes'] (and
-    out['octree_meshes_large'] for a 3-stage config), written as <out_dir>/octree/<index>.obj (octree_large/)."""
+    out['octree_meshes_large'] for a 3-stage config), written as <out_dir>/octree/<index>.obj (octree_large/).
+    views (needs mesh): also out['views'] = {position in the group: uint8 [20, view_size, view_size, 3]}, every
+    non-empty mesh (the cleaned one under mesh_clean) seen from the 20 FID views (render.render), written as
+    <out_dir>/fid_images/view_<j>/<index>.png -- the layout of the reference's generate_synth_image.py."""
     if mesh_clean and not mesh:
         raise ValueError('mesh_clean needs mesh')
+    if views and not mesh:
+        raise ValueError('views needs mesh')
     cs = CascadeSampler(net, cfg, vae)
     dev = cs.device
     for idxs in plan(n_shapes, rank, world, shapes_per_call):
@@ -111,6 +117,8 @@ def generate(net, cfg, n_shapes, rank, world, seed=0, ddim_steps=200, label=None
         dt = time.perf_counter() - t0
         if points:
             out['points'] = sample_points(out['meshes'], idxs, points, seed)
+        if views:
+            out['views'] = render_views(out['meshes'], view_size)
         if out_dir is not None:
             write_outputs(out_dir, idxs, out, cfg)
         yield idxs, out, dt
@@ -127,6 +135,17 @@ def sample_points(meshes, idxs, points, seed):
     return {b: pts[j] for j, b in enumerate(keep)}
 
 
+def render_views(meshes, size=299):
+    """{position: [20, size, size, 3] uint8} of the non-empty meshes of one group: generate_image_for_fid
+    (utils/render_utils.py:14-23) without the OBJ round trip."""
+    from . import render
+    keep = [b for b, (_, f) in enumerate(meshes) if f.shape[0] > 0]
+    if not keep:
+        return {}
+    images = render.render([meshes[b] for b in keep], size=size)
+    return {b: images[j] for j, b in enumerate(keep)}
+
+
 def write_outputs(out_dir, idxs, out, cfg):
     """Per shape: <index>/split_small.pth (+ split_large.pth) in the reference's sample-file format
     (tools/gen_split.py:50-54), <index>/sdf.pt when the SDF lattice was computed, and <index>.obj (export_mesh's
@@ -134,7 +153,7 @@ def write_outputs(out_dir, idxs, out, cfg):
     <index>.npy, its [points, 3] surface samples, when they were.  With the octree meshes: octree/<index>.obj
     (export_octree's file name, :376,420) and, for the large depth, octree_large/<index>.obj -- the reference writes
     both depths to octree/<index>.obj, so its depth-8 file replaces the depth-6 one
-    (octfusion_model_union_3t.py:172,191)."""
+    (octfusion_model_union_3t.py:172,191).  With the views: fid_images/view_<j>/<index>.png."""
     from .octree import octree2split_large, octree2split_small
     small = octree2split_small(out['octree_small'], cfg['full_depth'])
     large = bid = None
@@ -161,6 +180,9 @@ def write_outputs(out_dir, idxs, out, cfg):
                 mesh.write_obj(os.path.join(out_dir, sub, '%d.obj' % i), *out[key][b])
         if b in out.get('points', {}):
             np.save(os.path.join(out_dir, '%d.npy' % i), out['points'][b].cpu().numpy())
+        if b in out.get('views', {}):
+            from . import render
+            render.write_fid_images(os.path.join(out_dir, 'fid_images'), [i], out['views'][b][None])
 
 
 def run(args, rank, local_rank, world, device):
@@ -190,6 +212,11 @@ def run(args, rank, local_rank, world, device):
     kw = dict(mesh=True, mesh_level=args.mesh_level, mesh_scale=mesh_scale(args.config), points=points) if mesh else {}
     if clean:
         kw['mesh_clean'] = True
+    if getattr(args, 'views', False):
+        if not mesh or not args.out:
+            raise ValueError('--views needs --mesh and --out')
+        kw['views'] = True
+        kw['view_size'] = getattr(args, 'view_size', 299)
     if getattr(args, 'octree_mesh', False):
         if not args.out:
             raise ValueError('--octree-mesh needs --out')
@@ -245,9 +272,16 @@ def main(argv=None):
                     help='write the generated octree itself as a mesh of cubes, <out>/octree/<index>.obj (the '
                          'reference\'s export_octree) and, for a three-stage config, <out>/octree_large/<index>.obj; '
                          'needs --out, works with --no-vae')
+    ap.add_argument('--views', action='store_true',
+                    help='with --mesh: render every mesh (the cleaned one under --clean) from the 20 FID views on the '
+                         'device and write <out>/fid_images/view_<j>/<index>.png, the image set of the reference\'s '
+                         'generate_synth_image.py; needs --out')
+    ap.add_argument('--view-size', type=int, default=299, help='image size of --views (Inception v3: 299)')
     args = ap.parse_args(argv)
     if args.clean and not args.mesh:
         raise ValueError('--clean needs --mesh')
+    if args.views and not (args.mesh and args.out):
+        raise ValueError('--views needs --mesh and --out')
     if args.octree_mesh and not args.out:
         raise ValueError('--octree-mesh needs --out')
     rank, local_rank, world = dist.init()
