@@ -3,7 +3,11 @@
 // makes 3 scatter_add passes + 2 index_selects, ~7 passes).
 //
 // Statistics are accumulated per (batch element, channel) as fp64 (sum, sum of
-// squares): fp32 per-thread partials over <= 64 rows, fp64 across threads / blocks
+// squares): fp32 per-thread partials over the rows a thread owns of its block --
+// ceil(rows per block / rows per pass), rows per pass = 256 / (C / 4); a block owns 64
+// rows, or a multiple of 64 once there are more 64-row chunks than the block cap
+// (gn_stats_rows): 16 rows per thread at C = 256, 64 at C = 1024, 192 at C = 1024 with
+// 192-row blocks -- then fp64 across threads / blocks
 // (LDS then global atomics).  finalize reproduces the reference's arithmetic:
 // inv_count = 1/(count*cpg + eps), mean = S*inv_count, centred variance
 // sum((x-mean)^2)*inv_count = (SS - 2*mean*S + n*mean^2)*inv_count evaluated in

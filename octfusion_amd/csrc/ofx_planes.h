@@ -14,7 +14,7 @@ typedef const char __attribute__((address_space(1)))* gcp;
 typedef __attribute__((address_space(3))) void* ldsp;
 
 // ---- 16-bit operand pairs.  A value travels as hi + lo, both in the same 16-bit format:
-//   mode 2: bf16 pairs (8 + 8 significand bits: a = hi + lo to 2^-18 relative) -- "bf16x3";
+//   mode 2: bf16 pairs (8 + 8 significand bits: a = hi + lo to 2^-17 relative) -- "bf16x3";
 //   mode 3: fp16 pairs (11 + 11 bits: a = hi + lo to 2^-23 relative while lo is a normal fp16, to 2^-25 ABSOLUTE
 //           below -- v_mfma_f32_32x32x16_f16 honours fp16 denormal inputs on gfx950, tools/probes/mfma_f16_denorm.hip)
 //           -- "fp16x3": the same three MFMAs per product, ~30x less rounding than bf16x3.  Values beyond the fp16

@@ -1232,9 +1232,13 @@ def test_incremental_dual_octree(golden):
 
 @pytest.mark.gpu
 def test_gn_fused_rows_mappings():
-    """One-launch GroupNorm of the dense grids: the 16-channel block mapping (C = 64 .. 512) equals the one-block-per-group
-    mapping and torch.nn.functional.group_norm; odd widths (cpg 6 / 12: concatenated inputs) and short grids stay on the
-    per-group kernel; strided input / output (column slices of wider buffers)."""
+    """GroupNorm of the dense grids through ops.group_norm against torch.nn.functional.group_norm, under both settings of
+    ofx_set_gn_rows16, strided input / output (column slices of wider buffers).  At the default
+    ops.GN_ROWS_TWO_KERNELS = 2048, ops.group_norm calls ofx_gn_fused_rows only BELOW 2048 rows per batch element, and
+    the entry point picks the 16-channel kernel only FROM 2048 rows up: the rows = 512 / 64 / 1000 shapes reach the
+    one-block-per-group kernel (whatever the knob says), the rows = 4096 / 2304 / 2048 shapes run ofx_gn_stats_acc +
+    ofx_gn_apply twice, and no shape here launches gn_fused_rows16_kernel.  That kernel, and the dispatch conditions
+    of the entry point, are tested through the C ABI in tests/test_gpu_gn_entry.py (test_fused_rows)."""
     import torch.nn.functional as F
     from octfusion_amd import _lib, ops
     g = torch.Generator().manual_seed(9)
