@@ -886,6 +886,37 @@ int ofx_emd_matrix(const float* x, int64_t nx, const float* y, int64_t ny, int n
 /* the sampler's counter hash (host): splitmix64 steps h <- mix(h + 0x9E3779B97F4A7C15 * (x + 1)) over x = id, i, d */
 uint64_t ofx_metrics_hash(uint64_t seed, int64_t shape, int64_t point, int draw);
 
+/* ------------------------------------------------------------------ nearest-neighbour search (csrc/ofx_nnsearch.hip)
+ * Exact brute-force search over `batch` ragged cloud pairs, concatenated as ofx_surface_sample concatenates meshes:
+ * queries q [Q, 3] and targets t [T, 3] fp32; q_off, t_off [batch + 1] (int64 device) = where each pair's queries and
+ * targets begin, q_off[0] = t_off[0] = 0 and the last entry the total.  Host-known sizes for the launch geometry:
+ * total_q = Q, max_q / max_t = the largest query / target count of any pair (a pair larger than stated is not searched
+ * in full).  Outputs dist2 [Q] fp32 and idx [Q] int32, idx local to the pair's target cloud.  tests/
+ * recon_metrics_oracle.py restates the contract in float64.
+ *   distance  |q - t|^2 = fma(dz, dz, fma(dy, dy, dx * dx)) from direct differences in fp32.  Every pair of points goes
+ *     through that one code path: the value does not depend on which block, tile or slice saw it, and a cloud against
+ *     itself gives exactly 0.
+ *   tie rule  idx is the LOWEST index among the targets whose computed distance is minimal.
+ *   purity    (dist2, idx) is a pure function of the inputs: bitwise equal across repeats and across any `splits`.
+ *   edges     an empty target cloud gives dist2 = +inf, idx = -1; an empty query cloud writes nothing; batch == 0 or
+ *     Q == 0 launches nothing and returns OFX_OK.  max_t > INT32_MAX, more than INT32_MAX blocks, a negative size or a
+ *     NULL array that would be read or written: OFX_EINVAL, nothing launched.  Non-finite coordinates are the
+ *     caller's error (a NaN distance is never the minimum).
+ *   splits    the number of slices each pair's target cloud is cut into, every slice searched by blocks of its own.
+ *     0 = automatic: ofx_nn_search_splits(batch, max_q, max_t) = enough slices for about 1024 blocks (four per CU of
+ *     256), at most one per ofx_nn_search_tile() targets, at least 1 -- a single pair with few queries still fills the
+ *     chip.  k >= 1 forces k slices (for comparing geometries).  Slices combine through a 64-bit unsigned minimum of
+ *     (bits(dist2) << 32) | idx in ws (ofx_nn_search_ws_bytes(Q) bytes; may be NULL when one slice is used):
+ *     non-negative floats order as their bit patterns, equal distances by index, so the tie rule holds.
+ * A block searches ofx_nn_search_qpass() queries of one pair against one slice, in tiles of ofx_nn_search_tile(). */
+int ofx_nn_search_qpass(void);
+int ofx_nn_search_tile(void);
+int ofx_nn_search_splits(int batch, int64_t max_q, int64_t max_t);
+size_t ofx_nn_search_ws_bytes(int64_t total_q);
+int ofx_nn_search(const float* q, const int64_t* q_off, const float* t, const int64_t* t_off, int batch,
+                  int64_t total_q, int64_t max_q, int64_t max_t, int splits, void* ws, float* dist2, int32_t* idx,
+                  void* stream);
+
 /* ------------------------------------------------------------------ SDF training samples (csrc/ofx_sdfdata.hip)
  * The reference's tools/repair_mesh.py sample_sdf (:293-334) and sample_occu (:358-375) on an SDF lattice
  * sdf [S, S, S] fp32, x slowest (the reference's sdf[x, y, z]); tests/sdfdata_oracle.py restates both with numpy.

@@ -190,6 +190,11 @@ _SIGS = {
     'ofx_nn_matrix': (c_i, [c_p, c_l, c_i, c_p, c_l, c_i, c_p, c_p], True),
     'ofx_emd_matrix': (c_i, [c_p, c_l, c_p, c_l, c_i, c_i, c_p, c_p], True),
     'ofx_metrics_hash': (c_u64, [c_u64, c_l, c_l, c_i], False),
+    'ofx_nn_search_qpass': (c_i, [], False),
+    'ofx_nn_search_tile': (c_i, [], False),
+    'ofx_nn_search_splits': (c_i, [c_i, c_l, c_l], False),
+    'ofx_nn_search_ws_bytes': (c_sz, [c_l], False),
+    'ofx_nn_search': (c_i, [c_p, c_p, c_p, c_p, c_i, c_l, c_l, c_l, c_i, c_p, c_p, c_p, c_p], True),
     'ofx_sdf_sample_ws_bytes': (c_sz, [c_l, c_i], False),
     'ofx_sdf_sample_nodes': (c_i, [c_p, c_i, c_p, c_l, c_p, c_i, c_i, c_i, c_u64, c_l, c_p, c_f, c_p, c_p, c_p, c_p, c_p,
                                    c_p], True),

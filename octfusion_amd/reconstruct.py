@@ -16,6 +16,10 @@ octree_in, evaluate=True) -> get_sdfs -> export_mesh -> input.ply) and of ``calc
 * The score is calc_chamfer's pair: n surface samples of each side, not normalised, the two directed mean squared
   nearest-neighbour distances x 1e5.  The samples are the project's (counter hash), not trimesh's with seed 101.
 * A shape whose reconstruction is empty gets no OBJ and ``null`` scores, with a warning; the rest go on.
+* ``--metrics`` adds the reconstruction table of the occupancy-network line of work to every shape (Chamfer-L1 / -L2,
+  completeness, accuracy, normal consistency, F-score at ``--thresholds``) and ``--occupancy`` the volumetric IoU
+  against the ``points.npz`` beside a point-cloud input: octfusion_amd.recon_metrics, DESIGN.md 4.15.  Without them
+  metrics.json is what it was.
 
     python -m octfusion_amd.reconstruct --config snet_uncond --vae vae.pth --input data/02691156/1a04e3 --out recon
     python -m octfusion_amd.reconstruct --config snet_uncond --vae vae.pth --from-mesh --input samples/0.obj --out recon
@@ -29,7 +33,8 @@ import warnings
 import numpy as np
 import torch
 
-from . import configs, mesh, metrics, mpu
+from . import configs, mesh, metrics, mpu, recon_metrics
+from .metrics import sample_surface          # reconstruct() has an argument called metrics
 from .octree import Points, build_octree_batch
 
 CHAMFER_SCALE = 1.0e5           # utils/util_dualoctree.py:153
@@ -114,6 +119,11 @@ def _frame(verts):
     return (lo + hi) * 0.5, (2.0 / ext if ext > 0 else 1.0)
 
 
+def _input_dir(path):
+    """The directory of a point-cloud input: the path itself, or the one holding the ``pointcloud.npz`` it names."""
+    return os.path.dirname(path) if os.path.basename(os.path.normpath(path)) == 'pointcloud.npz' else path
+
+
 def _lap(timings, name, t0, device):
     if timings is None:
         return t0
@@ -126,19 +136,29 @@ def _lap(timings, name, t0, device):
 
 @torch.no_grad()
 def reconstruct(vae, cfg, inputs, device, sdf_resolution=256, sdf_scale=0.9, level=0.0, clean=False, batch=8, seed=0,
-                points=POINTS, chamfer_points=POINTS, fit=None, mpu_depth=None, out_dir=None, timings=None):
+                points=POINTS, chamfer_points=POINTS, fit=None, mpu_depth=None, out_dir=None, timings=None,
+                metrics=False, thresholds=recon_metrics.THRESHOLDS, occupancy=False):
     """Reconstruct every shape of ``inputs`` (read_inputs) through ``vae``, ``batch`` shapes per call.  cfg:
     recon_config(name), or a dict with depth, full_depth, point_scale.  points: samples per mesh input; fit: factor
     on the normalised mesh samples (default sdf_scale); mpu_depth: depth the SDF is read at (default depth_out);
     chamfer_points: samples per side of the score (0: no score).  The posterior noise comes from torch's generator,
     seeded with ``seed`` once at the start.  Writes <out_dir>/<name>/0.obj, <name>/input.ply and metrics.json when
-    out_dir is given.  Returns the metrics dict; ``result['meshes'][name]`` holds the device meshes."""
+    out_dir is given.  Returns the metrics dict; ``result['meshes'][name]`` holds the device meshes.
+    metrics: each shape's record gains ``scores`` = recon_metrics.surface_scores(gt, reconstruction) at ``thresholds``
+    (file units), with chamfer_points samples per mesh side (POINTS when chamfer_points is 0, so that
+    ``metrics=True, chamfer_points=0`` scores at 100 000 points without the single-block Chamfer launches); the gt side
+    is the input mesh in the output frame or, for a point-cloud input, the oriented input cloud x point_scale cut to
+    that count by the Chamfer score's stride rule; ``null`` for an empty reconstruction.  occupancy: a point-cloud
+    input whose directory holds ``points.npz`` gains ``iou``, ``iou_intersection``, ``iou_union`` =
+    recon_metrics.occupancy_iou of the batch's ``neural_mpu`` field against that file; any other input gets ``null``
+    and a warning; ``result['fields'][name]`` = (field, batch index)."""
     device = torch.device(device)
     ps = float(cfg['point_scale'])
     fit = float(sdf_scale if fit is None else fit)
     d_mpu = vae.depth_out if mpu_depth is None else int(mpu_depth)
     torch.manual_seed(seed)
-    shapes, meshes = {}, {}
+    shapes, meshes, fields = {}, {}, {}
+    score_points = chamfer_points if chamfer_points else POINTS
     for g0 in range(0, len(inputs), batch):
         group = inputs[g0:g0 + batch]
         t0 = time.perf_counter()
@@ -148,8 +168,8 @@ def reconstruct(vae, cfg, inputs, device, sdf_resolution=256, sdf_scale=0.9, lev
         if mesh_pos:
             vf = [(torch.from_numpy(group[k]['verts']).to(device), torch.from_numpy(group[k]['faces']).to(device))
                   for k in mesh_pos]
-            p, n = metrics.sample_surface(vf, n=points, seed=seed, normalize=True, ids=[g0 + k for k in mesh_pos],
-                                          normals=True)
+            p, n = sample_surface(vf, n=points, seed=seed, normalize=True, ids=[g0 + k for k in mesh_pos],
+                                  normals=True)
             for j, k in enumerate(mesh_pos):
                 clouds[k] = Points(p[j] * fit, n[j])
                 c, s = _frame(vf[j][0])
@@ -190,6 +210,31 @@ def reconstruct(vae, cfg, inputs, device, sdf_resolution=256, sdf_scale=0.9, lev
             shapes[name] = rec
             meshes[name] = (v, f)
         t0 = _lap(timings, 'chamfer', t0, device)
+        if metrics:
+            for k, it in enumerate(group):
+                (v, f), gt = recon[k], gts[k]
+                if gt is None:                        # the oriented cloud the encoder saw, in file units
+                    pts, nrm = clouds[k].points, clouds[k].normals
+                    if pts.shape[0] > score_points:
+                        sel = torch.arange(score_points, device=device) * pts.shape[0] // score_points
+                        pts, nrm = pts[sel], nrm[sel]
+                    gt = (pts * ps, nrm)
+                shapes[it['name']]['scores'] = None if f.shape[0] == 0 else recon_metrics.surface_scores(
+                    gt, (v, f), n=score_points, seed=seed, thresholds=thresholds)
+            t0 = _lap(timings, 'scores', t0, device)
+        if occupancy:
+            for k, it in enumerate(group):
+                rec = shapes[it['name']]
+                rec['iou'] = rec['iou_intersection'] = rec['iou_union'] = None
+                fields[it['name']] = (out['neural_mpu'], k)
+                occu = os.path.join(_input_dir(it['path']), 'points.npz') if it['kind'] == 'points' else None
+                if occu is None or not os.path.exists(occu):
+                    warnings.warn('reconstruct: %s: no points.npz beside the input, no IoU' % it['name'])
+                    continue
+                with np.load(occu) as z:
+                    rec['iou'], rec['iou_intersection'], rec['iou_union'] = recon_metrics.occupancy_iou(
+                        out['neural_mpu'], z['points'], z['occupancies'], ps, level=level, batch_index=k)
+            t0 = _lap(timings, 'iou', t0, device)
         if out_dir is not None:
             for k, it in enumerate(group):
                 d = os.path.join(out_dir, it['name'])
@@ -209,6 +254,8 @@ def reconstruct(vae, cfg, inputs, device, sdf_resolution=256, sdf_scale=0.9, lev
         with open(os.path.join(out_dir, 'metrics.json'), 'w') as fh:
             json.dump(res, fh, indent=1)
     res['meshes'] = meshes
+    if occupancy:
+        res['fields'] = fields
     return res
 
 
@@ -241,7 +288,17 @@ def parser():
                     help='surface samples per side of the Chamfer score (default: the --points default, a choice: '
                          'the reference never calls calc_chamfer); 0: no score.  The score of one shape is two '
                          'launches over N^2 point pairs, each on a single block of the device (DESIGN.md 4.9): '
-                         'the default is slow, 2048 is cheap')
+                         'the default is slow, 2048 is cheap; --metrics --chamfer-points 0 is the fast way to a '
+                         'Chamfer number at 100 000 points')
+    ap.add_argument('--metrics', action='store_true',
+                    help='add the reconstruction table to every shape (recon_metrics.surface_scores): Chamfer-L1/L2, '
+                         'completeness, accuracy, normal consistency, precision / recall / F-score, with '
+                         '--chamfer-points samples per side (%d when that is 0)' % POINTS)
+    ap.add_argument('--thresholds', type=float, nargs='+', default=list(recon_metrics.THRESHOLDS), metavar='T',
+                    help='with --metrics: the F-score distance thresholds, in file units')
+    ap.add_argument('--occupancy', action='store_true',
+                    help='add the volumetric IoU against the points.npz beside a pointcloud.npz input '
+                         '(recon_metrics.occupancy_iou)')
     return ap
 
 
@@ -249,6 +306,8 @@ def parse_args(argv=None):
     args = parser().parse_args(argv)
     if args.points < 1 or args.batch < 1 or args.chamfer_points < 0 or args.sdf_resolution < 2:
         raise ValueError('--points, --batch >= 1, --chamfer-points >= 0 and --sdf-resolution >= 2 are required')
+    if any(not t > 0 for t in args.thresholds):
+        raise ValueError('--thresholds must be positive')
     return args
 
 
@@ -275,8 +334,10 @@ def main(argv=None):
     res = reconstruct(vae, recon_config(args.config), inputs, device, sdf_resolution=args.sdf_resolution,
                       clean=args.clean, batch=args.batch, seed=args.seed, points=args.points,
                       chamfer_points=args.chamfer_points, fit=args.fit, mpu_depth=args.mpu_depth, out_dir=args.out,
-                      timings=timings)
+                      timings=timings, metrics=args.metrics, thresholds=tuple(args.thresholds),
+                      occupancy=args.occupancy)
     res.pop('meshes')
+    res.pop('fields', None)
     print(json.dumps(res))
     return res
 
