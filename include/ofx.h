@@ -978,7 +978,9 @@ int ofx_mesh_sdf_set_counters(unsigned long long* words);
 /* ------------------------------------------------------------------ rendering (csrc/ofx_render.hip)
  * Shaded views of triangle meshes for the reference's FID image sets (utils/render_utils.py:14-23, utils/render/):
  * a deterministic renderer of the project's own, parity with pyrender unpinned; tests/render_oracle.py
- * restates every stage.  `batch` meshes concatenated as for ofx_surface_sample: verts [V, 3] fp32, faces [F, 3] int32,
+ * restates every stage, tests/render_ms_oracle.py the multisampled entries (1, 4 or 16 samples per pixel; the
+ * one-sample entries are their samples = 1 case).
+ * `batch` meshes concatenated as for ofx_surface_sample: verts [V, 3] fp32, faces [F, 3] int32,
  * 0-based into the shape's own vertices (the caller checks them); offs (int64 device) = [vert_off[batch],
  * vert_cnt[batch], face_off[batch], face_cnt[batch]]; max_verts / max_faces = the largest count of one shape.
  * cam [views, 24] fp64 (device): per view the view matrix (world -> camera) and then the pose (camera -> world), each
@@ -1002,6 +1004,21 @@ int ofx_mesh_sdf_set_counters(unsigned long long* words);
  *   on equal quantised depth the lowest face index wins.  A triangle whose pixel box, clamped to the screen, holds
  *   more than big_px pixels goes to a list (ws: ofx_render_raster_ws_bytes) and is rasterised by a wave, the others
  *   by a thread: the keys do not depend on big_px.
+ * ofx_render_sample_offsets: xy [samples, 2] int32 (host) = the sample positions of a pixel in 1/256 pixel from its
+ *   origin (256 i, 256 j), samples in {1, 4, 16} (else OFX_EINVAL).  1: (128, 128), the centre.  4, the rotated grid:
+ *   (96, 32), (224, 96), (32, 160), (160, 224).  16: 128 + 16 o, o = (1,1), (-1,-3), (-3,2), (4,-1), (-5,-2), (2,5),
+ *   (5,3), (3,-5), (-2,6), (0,-7), (-4,-6), (-6,4), (-8,0), (7,-4), (6,7), (-7,-8): one sample in every one of the
+ *   pixel's 16 columns and 16 rows.  The kernels use this table.
+ * ofx_render_raster_ms: keys [batch, views, size, size, samples] uint64, the key of ofx_render_raster per sample:
+ *   sample s of pixel (i, j) sits at p = (256 i + x_s, 256 j + y_s), and coverage (with its tie rule, the winding swap
+ *   and the zero-area rule) and the depth are evaluated at p.  A triangle's pixel box takes in every pixel with a
+ *   sample inside its bounding box; big_px counts pixels, not samples, and ws is that of ofx_render_raster.  dropped
+ *   counts a triangle once per (shape, view).  samples = 1 is ofx_render_raster (the same code).
+ * ofx_render_shade_ms: per pixel, every distinct face among the pixel's samples is shaded once as ofx_render_shade
+ *   shades it, at the ray through the pixel's CENTRE (extrapolated on the face's plane where the centre is outside
+ *   it), so a face's colour in a pixel does not depend on which samples it won; a sample's colour c_s is that colour
+ *   clamped to [0, 1], or the background; image = floor(255 ((sum_s c_s) / samples) + 0.5), the sum in sample order
+ *   in fp64.  samples = 1 is ofx_render_shade (the same code).
  * ofx_render_shade: image [batch, views, size, size, 3] uint8 = floor(255 clamp(c, 0, 1) + 0.5); c is the background
  *   where the key is all ones, else the flat two-sided glTF 2.0 metallic-roughness shading of the key's triangle under
  *   a directional, a point and a spot light at the camera (DESIGN.md 4.14 has the closed form).  params (host, 13
@@ -1020,6 +1037,13 @@ int ofx_render_raster(const int32_t* faces, const int64_t* offs, int batch, int6
 int ofx_render_shade(const float* verts, const int32_t* faces, const int64_t* offs, int batch, const double* norm,
                      const double* cam, int views, int size, double tan_half_fov, const uint64_t* keys,
                      const double* params, uint8_t* image, void* stream);
+int ofx_render_sample_offsets(int samples, int32_t* xy);
+int ofx_render_raster_ms(const int32_t* faces, const int64_t* offs, int batch, int64_t total_verts, int64_t total_faces,
+                         int64_t max_faces, int views, int size, int samples, const int32_t* sxy, const double* depth,
+                         int64_t big_px, uint64_t* keys, int32_t* dropped, void* ws, void* stream);
+int ofx_render_shade_ms(const float* verts, const int32_t* faces, const int64_t* offs, int batch, const double* norm,
+                        const double* cam, int views, int size, int samples, double tan_half_fov, const uint64_t* keys,
+                        const double* params, uint8_t* image, void* stream);
 
 #ifdef __cplusplus
 }

@@ -206,6 +206,11 @@ _SIGS = {
     'ofx_render_raster_ws_bytes': (c_sz, [c_i, c_l], False),
     'ofx_render_raster': (c_i, [c_p, c_p, c_i, c_l, c_l, c_l, c_i, c_i, c_p, c_p, c_l, c_p, c_p, c_p, c_p], True),
     'ofx_render_shade': (c_i, [c_p, c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_d, c_p, ctypes.POINTER(c_d), c_p, c_p], True),
+    'ofx_render_sample_offsets': (c_i, [c_i, ctypes.POINTER(ctypes.c_int32)], True),
+    'ofx_render_raster_ms': (c_i, [c_p, c_p, c_i, c_l, c_l, c_l, c_i, c_i, c_i, c_p, c_p, c_l, c_p, c_p, c_p, c_p],
+                             True),
+    'ofx_render_shade_ms': (c_i, [c_p, c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_d, c_p, ctypes.POINTER(c_d), c_p, c_p],
+                            True),
 }
 
 EXPORTS = sorted(_SIGS)

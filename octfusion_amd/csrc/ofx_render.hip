@@ -3,13 +3,17 @@
 //   project  one block per mesh reduces the bounding box and the largest distance from its centre (min / max only: the
 //            result does not depend on order); one thread per (view, vertex) writes the screen position snapped to
 //            1/256 pixel and the window depth.
-//   raster   a 64-bit key per pixel, (depth quantised to 32 bits) << 32 | triangle id, resolved with atomicMin.
-//            Coverage is an integer function of the snapped coordinates (int64 edge functions at pixel centres,
-//            top-left rule); depth is float64 in individually rounded operations.  Small path: a thread per
-//            (view, triangle) walks the clamped pixel box; triangles whose box holds more than big_px pixels are
+//   raster   a 64-bit key per sample, (depth quantised to 32 bits) << 32 | triangle id, resolved with atomicMin.
+//            Coverage is an integer function of the snapped coordinates (int64 edge functions at the sample
+//            positions, top-left rule); depth is float64 in individually rounded operations.  Small path: a thread
+//            per (view, triangle) walks the clamped pixel box; triangles whose box holds more than big_px pixels are
 //            compacted with ballots into a list and rasterised one wave each.
-//   shade    per pixel, from the winning triangle: flat two-sided glTF metallic-roughness shading under three lights
-//            at the camera, in float64.
+//   shade    per pixel, from the winning triangles of its samples: flat two-sided glTF metallic-roughness shading
+//            under three lights at the camera, in float64, once per distinct face at the pixel-centre ray; the
+//            samples' colours are averaged in float64 and quantised once.
+//
+// 1, 4 or 16 samples per pixel (rd_sample: the one table).  The kernels are templates over the sample count; the
+// one-sample entry points are their S = 1 instances, where a pixel's only sample is its centre.
 //
 // tests/render_oracle.py restates every stage; all float64 arithmetic here is uncontracted and in the oracle's order.
 #include <float.h>
@@ -28,6 +32,19 @@ constexpr double RD_GUARD = 67108864.0;   // 2^26 sub-pixel units
 constexpr int32_t RD_DROPPED = INT32_MIN; // sx of a vertex whose triangles are dropped
 constexpr int RD_BIG_BLOCKS = 1024;       // blocks of the large path (4 waves each)
 constexpr uint64_t RD_EMPTY = ~0ull;
+
+// ---- sample positions: sub-pixel units from the pixel's origin (256 i, 256 j) --------------------------------------
+// 4: the rotated grid; 16: 128 + 16 o, one sample in every one of the pixel's 16 columns and 16 rows
+__host__ __device__ constexpr int rd_sample(int samples, int s, int axis) {
+  constexpr int g4[4][2] = {{96, 32}, {224, 96}, {32, 160}, {160, 224}};
+  constexpr int o16[16][2] = {{1, 1}, {-1, -3}, {-3, 2}, {4, -1}, {-5, -2}, {2, 5}, {5, 3}, {3, -5},
+                              {-2, 6}, {0, -7}, {-4, -6}, {-6, 4}, {-8, 0}, {7, -4}, {6, 7}, {-7, -8}};
+  return samples == 4 ? g4[s][axis] : samples == 16 ? RD_HALF + 16 * o16[s][axis] : RD_HALF;
+}
+__host__ __device__ constexpr int rd_sample_min(int samples) { return samples == 4 ? 32 : samples == 16 ? 0 : RD_HALF; }
+__host__ __device__ constexpr int rd_sample_max(int samples) {
+  return samples == 4 ? 224 : samples == 16 ? 240 : RD_HALF;
+}
 
 // ---- normalisation: centre of the bounding box, largest distance from it (scale_to_unit_sphere) --------------------
 __global__ __launch_bounds__(RD_NORM_T) void rd_norm_kernel(const float* __restrict__ verts,
@@ -144,6 +161,7 @@ __device__ __forceinline__ bool rd_owns(int64_t ax, int64_t ay, int64_t bx, int6
 __device__ __forceinline__ int rd_floor_div256(int64_t v) { return (int)(v >> 8); }   // arithmetic shift = floor
 
 // 0: fine, 1: dropped, 2: zero area
+template <int S>
 __device__ __forceinline__ int rd_setup(const int32_t* __restrict__ sxy, const double* __restrict__ depth, int64_t ia,
                                         int64_t ib, int64_t ic, int size, RdTri& t) {
   const int2 a = *reinterpret_cast<const int2*>(sxy + ia * 2);
@@ -164,36 +182,50 @@ __device__ __forceinline__ int rd_setup(const int32_t* __restrict__ sxy, const d
   t.area2 = area2;
   const int64_t xmin = min((int64_t)a.x, min((int64_t)b.x, (int64_t)c.x)), xmax = max((int64_t)a.x, max((int64_t)b.x, (int64_t)c.x));
   const int64_t ymin = min((int64_t)a.y, min((int64_t)b.y, (int64_t)c.y)), ymax = max((int64_t)a.y, max((int64_t)b.y, (int64_t)c.y));
-  // pixel i has its centre at 256 i + 128: the first centre >= min, the last <= max
-  t.x0 = max(rd_floor_div256(xmin - RD_HALF + RD_SUB - 1), 0);
-  t.y0 = max(rd_floor_div256(ymin - RD_HALF + RD_SUB - 1), 0);
-  t.x1 = min(rd_floor_div256(xmax - RD_HALF), size - 1);
-  t.y1 = min(rd_floor_div256(ymax - RD_HALF), size - 1);
+  // pixel i has its samples at 256 i + [omin, omax]: the first pixel whose last sample >= min, the last whose first
+  // sample <= max (one sample: the first centre >= min, the last <= max)
+  constexpr int omin = rd_sample_min(S), omax = rd_sample_max(S);
+  t.x0 = max(rd_floor_div256(xmin - omax + RD_SUB - 1), 0);
+  t.y0 = max(rd_floor_div256(ymin - omax + RD_SUB - 1), 0);
+  t.x1 = min(rd_floor_div256(xmax - omin), size - 1);
+  t.y1 = min(rd_floor_div256(ymax - omin), size - 1);
   return 0;
 }
 
-__device__ __forceinline__ void rd_pixel(const RdTri& t, int x, int y, uint32_t tri, uint64_t* __restrict__ row) {
-  const int64_t px = (int64_t)x * RD_SUB + RD_HALF, py = (int64_t)y * RD_SUB + RD_HALF;
-  const int64_t ea = rd_edge(t.bx, t.by, t.cx, t.cy, px, py);   // weight of a
-  const int64_t eb = rd_edge(t.cx, t.cy, t.ax, t.ay, px, py);   // weight of b
-  const int64_t ec = rd_edge(t.ax, t.ay, t.bx, t.by, px, py);   // weight of c
-  const bool in = (ea > 0 || (ea == 0 && rd_owns(t.bx, t.by, t.cx, t.cy))) &&
-                  (eb > 0 || (eb == 0 && rd_owns(t.cx, t.cy, t.ax, t.ay))) &&
-                  (ec > 0 || (ec == 0 && rd_owns(t.ax, t.ay, t.bx, t.by)));
-  if (!in) return;
-  // individually rounded, in this order.  Plain operators under this unit's `fp contract(off)`: the __dmul_rn /
-  // __dadd_rn intrinsics are inline functions compiled under the header's default contraction, and hipcc fuses them
-  // into v_fmac_f64 once they are inlined here.
-  const double s = ((double)ea * t.za + (double)eb * t.zb) + (double)ec * t.zc;
-  const double d = s / (double)t.area2;
-  double q = d * 4294967296.0;
-  if (!(q >= 0.0)) q = 0.0;
-  if (q > 4294967295.0) q = 4294967295.0;
-  const uint64_t key = ((uint64_t)(uint32_t)q << 32) | tri;
-  if (key < row[x]) atomicMin((unsigned long long*)(row + x), (unsigned long long)key);   // keys only ever decrease
+// px: the S keys of pixel (x, y).  The edge functions are affine: evaluated once, at sample 0, and stepped to the other
+// samples by exact int64 increments.
+template <int S>
+__device__ __forceinline__ void rd_pixel(const RdTri& t, int x, int y, uint32_t tri, uint64_t* __restrict__ px) {
+  const int64_t qx = (int64_t)x * RD_SUB + rd_sample(S, 0, 0), qy = (int64_t)y * RD_SUB + rd_sample(S, 0, 1);
+  const int64_t ea0 = rd_edge(t.bx, t.by, t.cx, t.cy, qx, qy);   // weight of a
+  const int64_t eb0 = rd_edge(t.cx, t.cy, t.ax, t.ay, qx, qy);   // weight of b
+  const int64_t ec0 = rd_edge(t.ax, t.ay, t.bx, t.by, qx, qy);   // weight of c
+  const bool oa = rd_owns(t.bx, t.by, t.cx, t.cy), ob = rd_owns(t.cx, t.cy, t.ax, t.ay),
+             oc = rd_owns(t.ax, t.ay, t.bx, t.by);
+  constexpr int unroll = S > 4 ? 4 : S;   // 16 samples unrolled whole hold 244 VGPRs, by fours 80
+#pragma unroll unroll
+  for (int s = 0; s < S; ++s) {
+    const int64_t dx = rd_sample(S, s, 0) - rd_sample(S, 0, 0), dy = rd_sample(S, s, 1) - rd_sample(S, 0, 1);
+    const int64_t ea = ea0 + ((t.cx - t.bx) * dy - (t.cy - t.by) * dx);
+    const int64_t eb = eb0 + ((t.ax - t.cx) * dy - (t.ay - t.cy) * dx);
+    const int64_t ec = ec0 + ((t.bx - t.ax) * dy - (t.by - t.ay) * dx);
+    const bool in = (ea > 0 || (ea == 0 && oa)) && (eb > 0 || (eb == 0 && ob)) && (ec > 0 || (ec == 0 && oc));
+    if (!in) continue;
+    // individually rounded, in this order.  Plain operators under this unit's `fp contract(off)`: the __dmul_rn /
+    // __dadd_rn intrinsics are inline functions compiled under the header's default contraction, and hipcc fuses
+    // them into v_fmac_f64 once they are inlined here.
+    const double z = ((double)ea * t.za + (double)eb * t.zb) + (double)ec * t.zc;
+    const double d = z / (double)t.area2;
+    double q = d * 4294967296.0;
+    if (!(q >= 0.0)) q = 0.0;
+    if (q > 4294967295.0) q = 4294967295.0;
+    const uint64_t key = ((uint64_t)(uint32_t)q << 32) | tri;
+    if (key < px[s]) atomicMin((unsigned long long*)(px + s), (unsigned long long)key);   // keys only ever decrease
+  }
 }
 
 // small path: grid (face blocks, mesh, view)
+template <int S>
 __global__ __launch_bounds__(RD_T) void rd_small_kernel(const int32_t* __restrict__ faces,
                                                         const int64_t* __restrict__ offs, int batch,
                                                         int64_t total_verts, int views, int size,
@@ -211,7 +243,7 @@ __global__ __launch_bounds__(RD_T) void rd_small_kernel(const int32_t* __restric
   if (f < nf) {
     const int32_t* F = faces + (offs[2 * batch + b] + f) * 3;
     const int64_t base = (int64_t)view * total_verts + offs[b];
-    state = rd_setup(sxy, depth, base + F[0], base + F[1], base + F[2], size, t);
+    state = rd_setup<S>(sxy, depth, base + F[0], base + F[1], base + F[2], size, t);
   }
   const uint64_t drop = __ballot(state == 1);
   if (drop && lane == 0) atomicAdd(dropped + b * views + view, (int)__popcll(drop));
@@ -226,12 +258,13 @@ __global__ __launch_bounds__(RD_T) void rd_small_kernel(const int32_t* __restric
     if (big) big_list[at + __popcll(bm & ((1ull << lane) - 1))] = ((uint64_t)(b * views + view) << 32) | (uint32_t)f;
   }
   if (!live || big) return;
-  uint64_t* img = keys + (int64_t)(b * views + view) * size * size;
+  uint64_t* img = keys + (int64_t)(b * views + view) * size * size * S;
   for (int y = t.y0; y <= t.y1; ++y)
-    for (int x = t.x0; x <= t.x1; ++x) rd_pixel(t, x, y, (uint32_t)f, img + (int64_t)y * size);
+    for (int x = t.x0; x <= t.x1; ++x) rd_pixel<S>(t, x, y, (uint32_t)f, img + ((int64_t)y * size + x) * S);
 }
 
 // large path: a wave per listed triangle, lanes over the pixels of its box
+template <int S>
 __global__ __launch_bounds__(RD_T) void rd_big_kernel(const int32_t* __restrict__ faces,
                                                       const int64_t* __restrict__ offs, int batch,
                                                       int64_t total_verts, int views, int size,
@@ -249,13 +282,13 @@ __global__ __launch_bounds__(RD_T) void rd_big_kernel(const int32_t* __restrict_
     const int32_t* F = faces + (offs[2 * batch + b] + f) * 3;
     const int64_t base = (int64_t)view * total_verts + offs[b];
     RdTri t;
-    if (rd_setup(sxy, depth, base + F[0], base + F[1], base + F[2], size, t) != 0) continue;   // (cannot happen)
+    if (rd_setup<S>(sxy, depth, base + F[0], base + F[1], base + F[2], size, t) != 0) continue;   // (cannot happen)
     const int w = t.x1 - t.x0 + 1;
     const int64_t npx = (int64_t)w * (t.y1 - t.y0 + 1);
-    uint64_t* img = keys + (int64_t)bv * size * size;
+    uint64_t* img = keys + (int64_t)bv * size * size * S;
     for (int64_t p = lane; p < npx; p += 64) {
       const int y = t.y0 + (int)(p / w), x = t.x0 + (int)(p % w);
-      rd_pixel(t, x, y, f, img + (int64_t)y * size);
+      rd_pixel<S>(t, x, y, f, img + ((int64_t)y * size + x) * S);
     }
   }
 }
@@ -301,6 +334,53 @@ __device__ __forceinline__ void rd_light(const RdShade& S, RdV3 N, RdV3 V, RdV3 
   }
 }
 
+// the unclamped colour of one face of mesh b at the ray through the centre of pixel (x, y), which need not hit it
+__device__ __forceinline__ void rd_face_colour(const RdShade& S, const float* __restrict__ V0,
+                                               const int32_t* __restrict__ F, const double* __restrict__ nrm,
+                                               const double* __restrict__ M, int x, int y, int size, double* col) {
+  const double s = nrm[3];
+  const RdV3 ctr = {nrm[0], nrm[1], nrm[2]};
+  RdV3 P3[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float* q = V0 + (int64_t)F[k] * 3;
+    P3[k] = {((double)q[0] - ctr.x) / s, ((double)q[1] - ctr.y) / s, ((double)q[2] - ctr.z) / s};
+  }
+  const RdV3 eye = {M[3], M[7], M[11]}, zax = {M[2], M[6], M[10]};
+  const double u = (((double)x + 0.5) / (double)size * 2.0 - 1.0) * S.tan_half;
+  const double v = (1.0 - ((double)y + 0.5) / (double)size * 2.0) * S.tan_half;
+  const RdV3 dir = {(M[0] * u + M[1] * v) - M[2], (M[4] * u + M[5] * v) - M[6], (M[8] * u + M[9] * v) - M[10]};
+  const RdV3 n = rd_cross(rd_sub(P3[1], P3[0]), rd_sub(P3[2], P3[0]));
+  const double den = rd_dot(n, dir);
+  RdV3 pos;
+  if (den != 0.0) {
+    const double t = rd_dot(n, rd_sub(P3[0], eye)) / den;
+    pos = {eye.x + t * dir.x, eye.y + t * dir.y, eye.z + t * dir.z};
+  } else {
+    pos = {((P3[0].x + P3[1].x) + P3[2].x) / 3.0, ((P3[0].y + P3[1].y) + P3[2].y) / 3.0,
+           ((P3[0].z + P3[1].z) + P3[2].z) / 3.0};
+  }
+  const RdV3 lv = rd_sub(eye, pos);
+  double d2 = rd_dot(lv, lv);
+  if (!(d2 >= 1e-12)) d2 = 1e-12;
+  const RdV3 V = rd_scale(lv, 1.0 / sqrt(d2));
+  const double nn = rd_dot(n, n);
+  RdV3 N = nn > 0.0 ? rd_scale(n, 1.0 / sqrt(nn)) : V;
+  if (rd_dot(N, V) < 0.0) N = {-N.x, -N.y, -N.z};
+  col[0] = col[1] = col[2] = 0.0;
+  rd_light(S, N, V, zax, S.i_dir, col);                       // directional: along the camera's -z
+  rd_light(S, N, V, V, S.i_point / d2, col);                  // point light at the eye
+  double sa = rd_dot(zax, V) * S.spot_scale + S.spot_offset;  // spot: axis -z, cone between inner and outer
+  sa = sa > 0.0 ? (sa < 1.0 ? sa : 1.0) : 0.0;
+  rd_light(S, N, V, V, (S.i_spot / d2) * (sa * sa), col);
+}
+
+// a NaN becomes 0
+__device__ __forceinline__ double rd_clamp01(double q) { return q > 0.0 ? (q < 1.0 ? q : 1.0) : 0.0; }
+
+// one thread per pixel: every distinct face among the pixel's NS samples is shaded once, each sample takes the clamped
+// colour of its face (or the background), and the mean, summed in sample order, is quantised once
+template <int NS>
 __global__ __launch_bounds__(RD_T) void rd_shade_kernel(const float* __restrict__ verts,
                                                         const int32_t* __restrict__ faces,
                                                         const int64_t* __restrict__ offs, int batch,
@@ -312,54 +392,41 @@ __global__ __launch_bounds__(RD_T) void rd_shade_kernel(const float* __restrict_
   const int64_t p = (int64_t)blockIdx.x * RD_T + threadIdx.x;
   if (p >= npix) return;
   const int bv = blockIdx.y, b = bv / views, view = bv - b * views;
-  const uint64_t key = keys[(int64_t)bv * npix + p];
+  const uint64_t* kp = keys + ((int64_t)bv * npix + p) * NS;
   uint8_t* o = image + ((int64_t)bv * npix + p) * 3;
-  double col[3] = {S.bg[0], S.bg[1], S.bg[2]};
-  if (key != RD_EMPTY) {
-    const int32_t* F = faces + (offs[2 * batch + b] + (int64_t)(uint32_t)key) * 3;
-    const float* V0 = verts + offs[b] * 3;
-    const double s = norm[b * 4 + 3];
-    const RdV3 ctr = {norm[b * 4], norm[b * 4 + 1], norm[b * 4 + 2]};
-    RdV3 P3[3];
+  const int y = (int)(p / size), x = (int)(p - (int64_t)y * size);
+  uint32_t id[NS];                  // the face of a sample; a face index is < 2^31, so all ones is the empty key
+  double col[NS][3];
+  uint32_t todo = 0;                // samples whose face is not shaded yet
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const float* q = V0 + (int64_t)F[k] * 3;
-      P3[k] = {((double)q[0] - ctr.x) / s, ((double)q[1] - ctr.y) / s, ((double)q[2] - ctr.z) / s};
-    }
-    const double* M = cam + (int64_t)view * 24 + 12;            // the pose: columns x, y, z axes and the eye
-    const RdV3 eye = {M[3], M[7], M[11]}, zax = {M[2], M[6], M[10]};
-    const int y = (int)(p / size), x = (int)(p - (int64_t)y * size);
-    const double u = (((double)x + 0.5) / (double)size * 2.0 - 1.0) * S.tan_half;
-    const double v = (1.0 - ((double)y + 0.5) / (double)size * 2.0) * S.tan_half;
-    const RdV3 dir = {(M[0] * u + M[1] * v) - M[2], (M[4] * u + M[5] * v) - M[6], (M[8] * u + M[9] * v) - M[10]};
-    const RdV3 n = rd_cross(rd_sub(P3[1], P3[0]), rd_sub(P3[2], P3[0]));
-    const double den = rd_dot(n, dir);
-    RdV3 pos;
-    if (den != 0.0) {
-      const double t = rd_dot(n, rd_sub(P3[0], eye)) / den;
-      pos = {eye.x + t * dir.x, eye.y + t * dir.y, eye.z + t * dir.z};
-    } else {
-      pos = {((P3[0].x + P3[1].x) + P3[2].x) / 3.0, ((P3[0].y + P3[1].y) + P3[2].y) / 3.0,
-             ((P3[0].z + P3[1].z) + P3[2].z) / 3.0};
-    }
-    const RdV3 lv = rd_sub(eye, pos);
-    double d2 = rd_dot(lv, lv);
-    if (!(d2 >= 1e-12)) d2 = 1e-12;
-    const RdV3 V = rd_scale(lv, 1.0 / sqrt(d2));
-    const double nn = rd_dot(n, n);
-    RdV3 N = nn > 0.0 ? rd_scale(n, 1.0 / sqrt(nn)) : V;
-    if (rd_dot(N, V) < 0.0) N = {-N.x, -N.y, -N.z};
-    col[0] = col[1] = col[2] = 0.0;
-    rd_light(S, N, V, zax, S.i_dir, col);                       // directional: along the camera's -z
-    rd_light(S, N, V, V, S.i_point / d2, col);                  // point light at the eye
-    double sa = rd_dot(zax, V) * S.spot_scale + S.spot_offset;  // spot: axis -z, cone between inner and outer
-    sa = sa > 0.0 ? (sa < 1.0 ? sa : 1.0) : 0.0;
-    rd_light(S, N, V, V, (S.i_spot / d2) * (sa * sa), col);
+  for (int s = 0; s < NS; ++s) {
+    id[s] = (uint32_t)kp[s];
+    if (id[s] != 0xFFFFFFFFu) todo |= 1u << s;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) col[s][c] = rd_clamp01(S.bg[c]);
+  }
+  while (todo) {                    // once per distinct face
+    const int first = __ffs(todo) - 1;
+    uint32_t face = id[0];
+#pragma unroll
+    for (int s = 1; s < NS; ++s) face = s == first ? id[s] : face;
+    double fc[3];
+    rd_face_colour(S, verts + offs[b] * 3, faces + (offs[2 * batch + b] + (int64_t)face) * 3, norm + b * 4,
+                   cam + (int64_t)view * 24 + 12, x, y, size, fc);
+#pragma unroll
+    for (int s = 0; s < NS; ++s)
+      if (((todo >> s) & 1u) && id[s] == face) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) col[s][c] = rd_clamp01(fc[c]);
+        todo &= ~(1u << s);
+      }
   }
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
-    double q = col[c];
-    q = q > 0.0 ? (q < 1.0 ? q : 1.0) : 0.0;                    // a NaN becomes 0
+    double q = col[0][c];
+#pragma unroll
+    for (int s = 1; s < NS; ++s) q = q + col[s][c];
+    q = q / (double)NS;
     o[c] = (uint8_t)floor(255.0 * q + 0.5);
   }
 }
@@ -395,35 +462,79 @@ extern "C" size_t ofx_render_raster_ws_bytes(int views, int64_t total_faces) {
   return 256 + (size_t)views * (size_t)total_faces * sizeof(uint64_t);
 }
 
-extern "C" int ofx_render_raster(const int32_t* faces, const int64_t* offs, int batch, int64_t total_verts,
-                                 int64_t total_faces, int64_t max_faces, int views, int size, const int32_t* sxy,
-                                 const double* depth, int64_t big_px, uint64_t* keys, int32_t* dropped, void* ws,
-                                 void* stream) {
-  if (!faces || !offs || !sxy || !depth || !keys || !dropped || !ws || !rd_args_ok(batch, total_verts, views, size) ||
-      total_faces < 1 || total_faces > INT32_MAX || max_faces < 1 || max_faces > total_faces || big_px < 0)
-    return OFX_EINVAL;
-  hipStream_t st = ofx_stream(stream);
+namespace {
+
+template <int S>
+int rd_raster(const int32_t* faces, const int64_t* offs, int batch, int64_t total_verts, int64_t max_faces, int views,
+              int size, const int32_t* sxy, const double* depth, int64_t big_px, uint64_t* keys, int32_t* dropped,
+              void* ws, hipStream_t st) {
   unsigned long long* big_count = (unsigned long long*)ws;
   uint64_t* big_list = (uint64_t*)((char*)ws + 256);
-  if (hipMemsetAsync(keys, 0xFF, (size_t)batch * views * size * size * sizeof(uint64_t), st) != hipSuccess ||
+  if (hipMemsetAsync(keys, 0xFF, (size_t)batch * views * size * size * S * sizeof(uint64_t), st) != hipSuccess ||
       hipMemsetAsync(dropped, 0, (size_t)batch * views * sizeof(int32_t), st) != hipSuccess ||
       hipMemsetAsync(big_count, 0, sizeof(unsigned long long), st) != hipSuccess)
     return OFX_ELAUNCH;
   const dim3 grid((unsigned)ofx_cdiv(max_faces, RD_T), (unsigned)batch, (unsigned)views);
-  rd_small_kernel<<<grid, RD_T, 0, st>>>(faces, offs, batch, total_verts, views, size, sxy, depth, big_px, keys, dropped,
-                                         big_count, big_list);
+  rd_small_kernel<S><<<grid, RD_T, 0, st>>>(faces, offs, batch, total_verts, views, size, sxy, depth, big_px, keys,
+                                            dropped, big_count, big_list);
   OFX_LAUNCH_CHECK();
-  rd_big_kernel<<<RD_BIG_BLOCKS, RD_T, 0, st>>>(faces, offs, batch, total_verts, views, size, sxy, depth, keys, big_count,
-                                                big_list);
+  rd_big_kernel<S><<<RD_BIG_BLOCKS, RD_T, 0, st>>>(faces, offs, batch, total_verts, views, size, sxy, depth, keys,
+                                                   big_count, big_list);
   OFX_LAUNCH_CHECK();
   return OFX_OK;
 }
 
-extern "C" int ofx_render_shade(const float* verts, const int32_t* faces, const int64_t* offs, int batch,
-                                const double* norm, const double* cam, int views, int size, double tan_half_fov,
-                                const uint64_t* keys, const double* params, uint8_t* image, void* stream) {
+template <int NS>
+int rd_shade(const float* verts, const int32_t* faces, const int64_t* offs, int batch, const double* norm,
+             const double* cam, int views, int size, const uint64_t* keys, const RdShade& S, uint8_t* image,
+             hipStream_t st) {
+  const dim3 grid((unsigned)ofx_cdiv((int64_t)size * size, RD_T), (unsigned)(batch * views));
+  rd_shade_kernel<NS><<<grid, RD_T, 0, st>>>(verts, faces, offs, batch, norm, cam, views, size, keys, S, image);
+  OFX_LAUNCH_CHECK();
+  return OFX_OK;
+}
+
+bool rd_samples_ok(int samples) { return samples == 1 || samples == 4 || samples == 16; }
+
+}  // namespace
+
+extern "C" int ofx_render_sample_offsets(int samples, int32_t* xy) {
+  if (!xy || !rd_samples_ok(samples)) return OFX_EINVAL;
+  for (int s = 0; s < samples; ++s) {
+    xy[s * 2] = rd_sample(samples, s, 0);
+    xy[s * 2 + 1] = rd_sample(samples, s, 1);
+  }
+  return OFX_OK;
+}
+
+extern "C" int ofx_render_raster_ms(const int32_t* faces, const int64_t* offs, int batch, int64_t total_verts,
+                                    int64_t total_faces, int64_t max_faces, int views, int size, int samples,
+                                    const int32_t* sxy, const double* depth, int64_t big_px, uint64_t* keys,
+                                    int32_t* dropped, void* ws, void* stream) {
+  if (!faces || !offs || !sxy || !depth || !keys || !dropped || !ws || !rd_args_ok(batch, total_verts, views, size) ||
+      total_faces < 1 || total_faces > INT32_MAX || max_faces < 1 || max_faces > total_faces || big_px < 0 ||
+      !rd_samples_ok(samples))
+    return OFX_EINVAL;
+  hipStream_t st = ofx_stream(stream);
+  auto raster = samples == 4 ? rd_raster<4> : samples == 16 ? rd_raster<16> : rd_raster<1>;
+  return raster(faces, offs, batch, total_verts, max_faces, views, size, sxy, depth, big_px, keys, dropped, ws, st);
+}
+
+extern "C" int ofx_render_raster(const int32_t* faces, const int64_t* offs, int batch, int64_t total_verts,
+                                 int64_t total_faces, int64_t max_faces, int views, int size, const int32_t* sxy,
+                                 const double* depth, int64_t big_px, uint64_t* keys, int32_t* dropped, void* ws,
+                                 void* stream) {
+  return ofx_render_raster_ms(faces, offs, batch, total_verts, total_faces, max_faces, views, size, 1, sxy, depth,
+                              big_px, keys, dropped, ws, stream);
+}
+
+extern "C" int ofx_render_shade_ms(const float* verts, const int32_t* faces, const int64_t* offs, int batch,
+                                   const double* norm, const double* cam, int views, int size, int samples,
+                                   double tan_half_fov, const uint64_t* keys, const double* params, uint8_t* image,
+                                   void* stream) {
   if (!verts || !faces || !offs || !norm || !cam || !keys || !params || !image || batch < 1 || views < 1 ||
-      (int64_t)batch * views > 65535 || size < 1 || size > OFX_RENDER_MAX_SIZE || !(tan_half_fov > 0.0))
+      (int64_t)batch * views > 65535 || size < 1 || size > OFX_RENDER_MAX_SIZE || !(tan_half_fov > 0.0) ||
+      !rd_samples_ok(samples))
     return OFX_EINVAL;
   RdShade S;
   for (int c = 0; c < 3; ++c) S.base[c] = params[c];
@@ -436,9 +547,14 @@ extern "C" int ofx_render_shade(const float* verts, const int32_t* faces, const 
   S.spot_offset = params[9];
   for (int c = 0; c < 3; ++c) S.bg[c] = params[10 + c];
   S.tan_half = tan_half_fov;
-  const dim3 grid((unsigned)ofx_cdiv((int64_t)size * size, RD_T), (unsigned)(batch * views));
-  rd_shade_kernel<<<grid, RD_T, 0, ofx_stream(stream)>>>(verts, faces, offs, batch, norm, cam, views, size, keys, S,
-                                                         image);
-  OFX_LAUNCH_CHECK();
-  return OFX_OK;
+  hipStream_t st = ofx_stream(stream);
+  auto shade = samples == 4 ? rd_shade<4> : samples == 16 ? rd_shade<16> : rd_shade<1>;
+  return shade(verts, faces, offs, batch, norm, cam, views, size, keys, S, image, st);
+}
+
+extern "C" int ofx_render_shade(const float* verts, const int32_t* faces, const int64_t* offs, int batch,
+                                const double* norm, const double* cam, int views, int size, double tan_half_fov,
+                                const uint64_t* keys, const double* params, uint8_t* image, void* stream) {
+  return ofx_render_shade_ms(verts, faces, offs, batch, norm, cam, views, size, 1, tan_half_fov, keys, params, image,
+                             stream);
 }

@@ -81,7 +81,8 @@ def prepare(config, rank, device, ckpt=None, vae_ckpt=None, with_vae=True, allow
 
 def generate(net, cfg, n_shapes, rank, world, seed=0, ddim_steps=200, label=None, vae=None, out_dir=None,
              shapes_per_call=1, use_graph=None, sdf_resolution=None, timings=None, mesh=False, mesh_level=0.0,
-             mesh_scale=1.0, points=None, mesh_clean=False, octree_mesh=False, views=False, view_size=299):
+             mesh_scale=1.0, points=None, mesh_clean=False, octree_mesh=False, views=False, view_size=299,
+             view_samples=1):
     """Yields (result indices, output dict, seconds) for every group of shapes this rank owns.  mesh: also
     out['meshes'] (needs the VAE and sdf_resolution), written as <out_dir>/<index>.obj.  points (needs mesh): also
     out['points'] = {position in the group: [points, 3] cloud} of every non-empty mesh, sampled on the device after the
@@ -90,7 +91,8 @@ def generate(net, cfg, n_shapes, rank, world, seed=0, ddim_steps=200, label=None
     out['mesh_components'] holds the component counts before cleaning.  octree_mesh: also out['octree_meshes'] (and
     out['octree_meshes_large'] for a 3-stage config), written as <out_dir>/octree/<index>.obj (octree_large/).
     views (needs mesh): also out['views'] = {position in the group: uint8 [20, view_size, view_size, 3]}, every
-    non-empty mesh (the cleaned one under mesh_clean) seen from the 20 FID views (render.render), written as
+    non-empty mesh (the cleaned one under mesh_clean) seen from the 20 FID views (render.render, view_samples samples
+    per pixel), written as
     <out_dir>/fid_images/view_<j>/<index>.png -- the layout of the reference's generate_synth_image.py."""
     if mesh_clean and not mesh:
         raise ValueError('mesh_clean needs mesh')
@@ -118,7 +120,7 @@ def generate(net, cfg, n_shapes, rank, world, seed=0, ddim_steps=200, label=None
         if points:
             out['points'] = sample_points(out['meshes'], idxs, points, seed)
         if views:
-            out['views'] = render_views(out['meshes'], view_size)
+            out['views'] = render_views(out['meshes'], view_size, view_samples)
         if out_dir is not None:
             write_outputs(out_dir, idxs, out, cfg)
         yield idxs, out, dt
@@ -135,14 +137,14 @@ def sample_points(meshes, idxs, points, seed):
     return {b: pts[j] for j, b in enumerate(keep)}
 
 
-def render_views(meshes, size=299):
+def render_views(meshes, size=299, samples=1):
     """{position: [20, size, size, 3] uint8} of the non-empty meshes of one group: generate_image_for_fid
     (utils/render_utils.py:14-23) without the OBJ round trip."""
     from . import render
     keep = [b for b, (_, f) in enumerate(meshes) if f.shape[0] > 0]
     if not keep:
         return {}
-    images = render.render([meshes[b] for b in keep], size=size)
+    images = render.render([meshes[b] for b in keep], size=size, samples=samples)
     return {b: images[j] for j, b in enumerate(keep)}
 
 
@@ -217,6 +219,7 @@ def run(args, rank, local_rank, world, device):
             raise ValueError('--views needs --mesh and --out')
         kw['views'] = True
         kw['view_size'] = getattr(args, 'view_size', 299)
+        kw['view_samples'] = getattr(args, 'view_samples', 1)
     if getattr(args, 'octree_mesh', False):
         if not args.out:
             raise ValueError('--octree-mesh needs --out')
@@ -277,6 +280,8 @@ def main(argv=None):
                          'device and write <out>/fid_images/view_<j>/<index>.png, the image set of the reference\'s '
                          'generate_synth_image.py; needs --out')
     ap.add_argument('--view-size', type=int, default=299, help='image size of --views (Inception v3: 299)')
+    ap.add_argument('--view-samples', type=int, default=1, choices=(1, 4, 16),
+                    help='samples per pixel of --views (render.render samples=; 4 is recommended for FID image sets)')
     args = ap.parse_args(argv)
     if args.clean and not args.mesh:
         raise ValueError('--clean needs --mesh')

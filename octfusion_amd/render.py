@@ -11,7 +11,11 @@ screen coordinates snapped to 1/256 pixel -- and its parity with pyrender is unp
 two image sets, so draw BOTH the generated set and the dataset set with it.  The FID number itself is computed outside
 the project (the folders feed the reference's metrics/calc_fid.py unchanged).
 
-    python -m octfusion_amd.render --input meshes/ --out fid_images [--size 299] [--batch 8]
+``samples`` = 4 or 16 draws multisampled: coverage and depth per sample, one flat shade per face and pixel at the
+pixel-centre ray, the samples averaged and quantised once.  The reference's pyrender is believed to resolve a 4-sample
+framebuffer, so draw both FID sets with ``--samples 4``; the default stays 1.
+
+    python -m octfusion_amd.render --input meshes/ --out fid_images [--size 299] [--batch 8] [--samples 4]
 """
 import argparse
 import ctypes
@@ -34,6 +38,7 @@ BIG_PX = 32                 # a triangle whose clamped pixel box holds more pixe
 WORKSPACE_BYTES = 1 << 30   # key buffer + projected vertices + large-triangle list of one chunk of views stay below
 # the reference's three lights at the camera (render_utils.py:88-99, called with intensity 3.0) and the material
 # believed to be pyrender's default for a mesh without one -- parameters, because that cannot be pinned here
+SAMPLES = (1, 4, 16)        # samples per pixel; the positions are the library's (sample_offsets)
 MATERIAL = dict(base_color=(0.3, 0.3, 0.3), metallic=0.2, roughness=0.8, directional=3.0, point=6.0, spot=3.0,
                 spot_inner=math.pi / 16, spot_outer=math.pi / 6)
 
@@ -117,6 +122,21 @@ def shade_params(background=1.0, **material):
     return [float(x) for x in vals]
 
 
+def sample_offsets(samples):
+    """[samples, 2] int32: the sample positions of a pixel in 1/256 pixel from its origin, read from the library
+    (ofx_render_sample_offsets) so that they are the kernels' own."""
+    samples = _check_samples(samples)
+    xy = (ctypes.c_int32 * (2 * samples))()
+    _lib.call('ofx_render_sample_offsets', samples, xy)
+    return np.asarray(list(xy), np.int32).reshape(samples, 2)
+
+
+def _check_samples(samples):
+    if isinstance(samples, bool) or samples not in SAMPLES:
+        raise ValueError('render: samples must be one of %s, got %r' % (SAMPLES, samples))
+    return int(samples)
+
+
 def _device():
     return torch.device('cuda', torch.cuda.current_device())
 
@@ -157,13 +177,13 @@ def _gather(meshes):
     return V, F, nv, nf
 
 
-def _views_per_chunk(B, n_views, size, total_verts, total_faces):
-    per_view = B * size * size * 8 + total_verts * 16 + total_faces * 8
+def _views_per_chunk(B, n_views, size, total_verts, total_faces, samples=1):
+    per_view = B * size * size * 8 * samples + total_verts * 16 + total_faces * 8
     return max(1, min(n_views, WORKSPACE_BYTES // per_view, 65535 // B))
 
 
 def render(meshes, poses=None, size=299, normalize=True, background=1.0, buffers=False, big_px=None, znear=ZNEAR,
-           zfar=ZFAR, **material):
+           zfar=ZFAR, samples=1, **material):
     """uint8 [B, V, size, size, 3] device tensor: every mesh of ``meshes`` -- the list ``mesh.marching_cubes`` returns,
     or ``(verts, faces)`` pairs (numpy or tensors, faces 0-based) -- seen from every pose of ``poses`` ([V, 4, 4]
     camera-to-world, rigid; None: the 20 FID views).
@@ -176,9 +196,16 @@ def render(meshes, poses=None, size=299, normalize=True, background=1.0, buffers
     float64 [V, total verts] (the projected vertices of the concatenated meshes), ``norm`` float64 [B, 4] (centre,
     scale) and ``dropped`` int32 [B, V] (triangles dropped at the near plane or the guard band).
 
+    samples: 1 (the pixel centre), 4 (rotated grid) or 16 samples per pixel.  With more than one, coverage and depth
+    are resolved per sample, every face is shaded once per pixel at the pixel-centre ray, and the pixel is the mean of
+    its samples' colours, quantised once; ``ids`` and ``depth`` gain a trailing ``samples`` axis and the dict carries
+    ``sample_offsets`` int32 [samples, 2] (1/256 pixel from the pixel's origin).  Any other value raises ValueError
+    before any launch.
+
     Views are rendered in chunks so that the key buffer, the projected vertices and the large-triangle list of one
     chunk stay under WORKSPACE_BYTES (a single view may exceed it).  One host synchronisation, for the face-index
     check; a bad mesh raises ValueError naming the shape before any launch, OfxError without a GPU."""
+    samples = _check_samples(samples)
     _lib.require_device()
     size = int(size)
     if not 1 <= size <= 4096:
@@ -202,14 +229,16 @@ def render(meshes, poses=None, size=299, normalize=True, background=1.0, buffers
     offs = torch.tensor(np.concatenate([voff, nv, foff, nf]), dtype=torch.int64).to(dev)
     tan_half = math.tan(YFOV / 2.0)
     st = _lib.stream()
-    chunk = _views_per_chunk(B, n_views, size, tv, tf)
+    chunk = _views_per_chunk(B, n_views, size, tv, tf, samples)
+    ms = samples > 1                # one sample: the one-sample entry points, and buffers without the samples axis
+    kshape = (size, size, samples) if ms else (size, size)
     image = torch.empty(B, n_views, size, size, 3, dtype=torch.uint8, device=dev)
     norm = torch.empty(B, 4, dtype=torch.float64, device=dev)
     keep = {k: [] for k in ('keys', 'sxy', 'vertex_depth', 'dropped')} if buffers else None
     nc = min(chunk, n_views)
     sxy = torch.empty(nc, tv, 2, dtype=torch.int32, device=dev)
     vdepth = torch.empty(nc, tv, dtype=torch.float64, device=dev)
-    keys = torch.empty(B, nc, size, size, dtype=torch.int64, device=dev)
+    keys = torch.empty(B, nc, *kshape, dtype=torch.int64, device=dev)
     dropped = torch.empty(B, nc, dtype=torch.int32, device=dev)
     img = image if nc == n_views else torch.empty(B, nc, size, size, 3, dtype=torch.uint8, device=dev)
     ws = torch.empty(_lib.lib().ofx_render_raster_ws_bytes(nc, tf), dtype=torch.uint8, device=dev)
@@ -218,15 +247,21 @@ def render(meshes, poses=None, size=299, normalize=True, background=1.0, buffers
         cam = torch.from_numpy(np.ascontiguousarray(cam_all[v0:v0 + n])).to(dev)
         _lib.call('ofx_render_project', _lib.ptr(V), _lib.ptr(offs), B, tv, max(nv), _lib.ptr(cam), n, size, tan_half,
                   float(znear), float(zfar), 1 if normalize else 0, _lib.ptr(norm), _lib.ptr(sxy), _lib.ptr(vdepth), st)
-        _lib.call('ofx_render_raster', _lib.ptr(F), _lib.ptr(offs), B, tv, tf, max(nf), n, size, _lib.ptr(sxy),
-                  _lib.ptr(vdepth), big_px, _lib.ptr(keys), _lib.ptr(dropped), _lib.ptr(ws), st)
-        _lib.call('ofx_render_shade', _lib.ptr(V), _lib.ptr(F), _lib.ptr(offs), B, _lib.ptr(norm), _lib.ptr(cam), n,
-                  size, tan_half, _lib.ptr(keys), params, _lib.ptr(img), st)
+        if ms:
+            _lib.call('ofx_render_raster_ms', _lib.ptr(F), _lib.ptr(offs), B, tv, tf, max(nf), n, size, samples,
+                      _lib.ptr(sxy), _lib.ptr(vdepth), big_px, _lib.ptr(keys), _lib.ptr(dropped), _lib.ptr(ws), st)
+            _lib.call('ofx_render_shade_ms', _lib.ptr(V), _lib.ptr(F), _lib.ptr(offs), B, _lib.ptr(norm), _lib.ptr(cam),
+                      n, size, samples, tan_half, _lib.ptr(keys), params, _lib.ptr(img), st)
+        else:
+            _lib.call('ofx_render_raster', _lib.ptr(F), _lib.ptr(offs), B, tv, tf, max(nf), n, size, _lib.ptr(sxy),
+                      _lib.ptr(vdepth), big_px, _lib.ptr(keys), _lib.ptr(dropped), _lib.ptr(ws), st)
+            _lib.call('ofx_render_shade', _lib.ptr(V), _lib.ptr(F), _lib.ptr(offs), B, _lib.ptr(norm), _lib.ptr(cam), n,
+                      size, tan_half, _lib.ptr(keys), params, _lib.ptr(img), st)
         # a short last chunk fills the head of the flat buffers: [B, n, ...] views of them
         if img is not image:
             image[:, v0:v0 + n] = img.view(-1)[:B * n * size * size * 3].view(B, n, size, size, 3)
         if buffers:
-            keep['keys'].append(keys.view(-1)[:B * n * size * size].view(B, n, size, size).clone())
+            keep['keys'].append(keys.view(-1)[:B * n * size * size * samples].view(B, n, *kshape).clone())
             keep['sxy'].append(sxy.view(-1)[:n * tv * 2].view(n, tv, 2).clone())
             keep['vertex_depth'].append(vdepth.view(-1)[:n * tv].view(n, tv).clone())
             keep['dropped'].append(dropped.view(-1)[:B * n].view(B, n).clone())
@@ -236,8 +271,11 @@ def render(meshes, poses=None, size=299, normalize=True, background=1.0, buffers
     ids = (k & 0xFFFFFFFF).to(torch.int32)          # 0xFFFFFFFF wraps to -1: the background
     dq = (k >> 32) & 0xFFFFFFFF
     depth = torch.where(k == -1, torch.ones((), dtype=torch.float64, device=dev), dq.to(torch.float64) / 4294967296.0)
-    return image, dict(ids=ids, depth=depth, sxy=torch.cat(keep['sxy'], 0), vertex_depth=torch.cat(keep['vertex_depth'], 0),
-                       norm=norm, dropped=torch.cat(keep['dropped'], 1))
+    out = dict(ids=ids, depth=depth, sxy=torch.cat(keep['sxy'], 0), vertex_depth=torch.cat(keep['vertex_depth'], 0),
+               norm=norm, dropped=torch.cat(keep['dropped'], 1))
+    if ms:
+        out['sample_offsets'] = torch.from_numpy(sample_offsets(samples)).to(dev)
+    return image, out
 
 
 # ---- PNG files (zlib + struct only) --------------------------------------------------------------------------------
@@ -295,6 +333,8 @@ def main(argv=None):
     ap.add_argument('--out', required=True)
     ap.add_argument('--size', type=int, default=299)
     ap.add_argument('--batch', type=int, default=8, help='meshes per render call')
+    ap.add_argument('--samples', type=int, default=1, choices=SAMPLES,
+                    help='samples per pixel (4: what the reference\'s pyrender is believed to resolve)')
     args = ap.parse_args(argv)
     from . import mesh
     _lib.require_device()
@@ -307,11 +347,11 @@ def main(argv=None):
     dropped = 0
     for g0 in range(0, len(files), args.batch):
         group = files[g0:g0 + args.batch]
-        images, buf = render([mesh.read_obj(f) for f in group], size=args.size, buffers=True)
+        images, buf = render([mesh.read_obj(f) for f in group], size=args.size, buffers=True, samples=args.samples)
         dropped += int(buf['dropped'].sum())
         write_fid_images(args.out, [os.path.splitext(os.path.basename(f))[0] for f in group], images)
-    res = {'shapes': len(files), 'views': 20, 'size': args.size, 'seconds': time.perf_counter() - t0,
-           'dropped_triangles': dropped}
+    res = {'shapes': len(files), 'views': 20, 'size': args.size, 'samples': args.samples,
+           'seconds': time.perf_counter() - t0, 'dropped_triangles': dropped}
     print(json.dumps(res))
     return res
 

@@ -1,13 +1,14 @@
 """Time octfusion_amd.render on the device: 8 marching-cubes meshes from 256^3 lattices x 20 views x
 299^2, and a low-polygon mesh of large triangles as raw dataset meshes have them.
 
-    python tools/render_probe.py [--out DIR] [--runs 12] [--lattice 256]
+    python tools/render_probe.py [--out DIR] [--runs 12] [--lattice 256] [--samples 1|4|16]
 
 Device events around `render` after two warm calls, the median of --runs; then one more call with every entry point
 between its own events (_lib.PROFILE).  Bytes are the algorithm's compulsory traffic from the shapes, not a counter:
   project  per view: read verts 12 B, write sxy + depth 16 B, per vertex
-  raster   per view: read a face 12 B and its three projected vertices 3 x 16 B, per face; fill the keys 8 B per pixel
-  shade    read a key 8 B, write 3 B, per pixel; a covered pixel also reads a face 12 B and three vertices 36 B
+  raster   per view: read a face 12 B and its three projected vertices 3 x 16 B, per face; fill the keys 8 B per sample
+  shade    read the keys 8 B per sample, write 3 B, per pixel; a covered pixel also reads a face 12 B and three vertices
+           36 B (once: further faces of a multisampled pixel are not counted)
 Prints one JSON line and, with --out, writes it to DIR/render_probe.json.
 """
 import argparse
@@ -94,22 +95,26 @@ def stages(fn):
     return out
 
 
-def traffic(meshes, views, size, covered):
+def traffic(meshes, views, size, covered, samples=1):
     nv = sum(int(v.shape[0]) for v, _ in meshes)
     nf = sum(int(f.shape[0]) for _, f in meshes)
     px = len(meshes) * views * size * size
-    return {'project': views * nv * 28, 'raster': views * nf * 60 + px * 8, 'shade': px * 11 + covered * 48}
+    return {'project': views * nv * 28, 'raster': views * nf * 60 + px * 8 * samples,
+            'shade': px * (8 * samples + 3) + covered * 48}
 
 
 def measure(meshes, size, runs, **kw):
     ms = timed(lambda: render.render(meshes, size=size, **kw), runs)
     st = stages(lambda: render.render(meshes, size=size, **kw))
     _, buf = render.render(meshes, size=size, buffers=True, **kw)
-    covered = int((buf['ids'] >= 0).sum())
-    by = traffic(meshes, 20, size, covered)
+    samples = kw.get('samples', 1)
+    hit = buf['ids'] >= 0
+    covered = int((hit.any(-1) if samples > 1 else hit).sum())
+    by = traffic(meshes, 20, size, covered, samples)
     med = statistics.median(ms)
     return {'meshes': len(meshes), 'vertices': sum(int(v.shape[0]) for v, _ in meshes),
-            'faces': sum(int(f.shape[0]) for _, f in meshes), 'size': size, 'runs_ms': [round(m, 3) for m in ms],
+            'faces': sum(int(f.shape[0]) for _, f in meshes), 'size': size, 'samples': samples,
+            'runs_ms': [round(m, 3) for m in ms],
             'median_ms': med, 'min_ms': min(ms), 'max_ms': max(ms), 'stage_ms': st, 'bytes': by,
             'bytes_total': sum(by.values()), 'hbm_fraction': sum(by.values()) / (med * 1e-3) / HBM_PEAK,
             'covered_pixels': covered, 'dropped': int(buf['dropped'].sum())}
@@ -121,16 +126,18 @@ def main(argv=None):
     ap.add_argument('--runs', type=int, default=12)
     ap.add_argument('--lattice', type=int, default=256)
     ap.add_argument('--shapes', type=int, default=8)
+    ap.add_argument('--samples', type=int, default=1, choices=render.SAMPLES, help='samples per pixel')
     args = ap.parse_args(argv)
     _lib.require_device()
     dev = torch.device('cuda', torch.cuda.current_device())
     res = {}
     meshes = mesh.marching_cubes(lattices(args.shapes, args.lattice, dev))
-    res['marching_cubes_%d' % args.lattice] = measure(meshes, 299, args.runs)
+    kw = {'samples': args.samples} if args.samples > 1 else {}
+    res['marching_cubes_%d' % args.lattice] = measure(meshes, 299, args.runs, **kw)
     v, f = low_poly()
     lp = [(torch.from_numpy(v).to(dev), torch.from_numpy(f).to(dev))] * args.shapes
-    res['low_poly'] = measure(lp, 299, args.runs)
-    res['low_poly_all_threads'] = measure(lp, 299, args.runs, big_px=2 ** 40)
+    res['low_poly'] = measure(lp, 299, args.runs, **kw)
+    res['low_poly_all_threads'] = measure(lp, 299, args.runs, big_px=2 ** 40, **kw)
     line = json.dumps(res)
     print(line)
     if args.out:
