@@ -822,6 +822,38 @@ int ofx_mesh_cc_extract(const float* verts, const int32_t* faces, const int64_t*
                         const int64_t* new_tri_off, float* out_verts, int32_t* out_faces, void* ws,
                         const int32_t* status, void* stream);
 
+/* ------------------------------------------------------------------ mesh simplification (csrc/ofx_simplify.hip)
+ * Vertex clustering with quadric-error placement (Lindstrom 2000): the decimation users of the reference run on the
+ * host after export_mesh.  tests/simplify_oracle.py restates the rule with numpy; DESIGN.md section 4.16 derives it.
+ * Input: a batch mesh in the layout of the component calls above (verts [V, 3] fp32, faces [F, 3] int32 local to each
+ * shape, vert_off / tri_off int64 [batch + 1]).  Limits: batch >= 1, 1 <= total_verts < INT32_MAX,
+ * 1 <= total_faces <= INT32_MAX / 3 (ofx_simplify_ws_bytes returns 0 outside).  `ws` is one workspace of
+ * ofx_simplify_ws_bytes bytes shared by the two calls; `status` is two int32 the caller reads back with the counts:
+ * status[0] != 0 a face index outside its shape's [0, n_verts) (bit 0) or inconsistent offsets (bit 1) -- checked
+ * before any index is followed, and then no later pass touches the mesh; status[1] != 0 a vertex needs a cell index
+ * >= 1024 under cell_size (the outputs are not to be used).  Nothing allocates, nothing synchronises, no
+ * floating-point atomics: the output is a function of each shape's own vertices and faces, bitwise reproducible, the
+ * same alone or anywhere in a batch.
+ * ofx_simplify_cluster: the grid is `cells` (1 .. 1024) cells along the longest side of each shape's bounding box, or,
+ *   with cells == 0, cells of side cell_size (finite, > 0); 0 < reg <= 1 is the regulariser of the placement.  All
+ *   arithmetic is fp64.  counts int64 [batch, 8]: occupied cells (clusters), kept vertices, kept faces, faces that
+ *   collapsed (fewer than three different clusters), faces dropped as duplicates of an earlier face, 1 if the shape
+ *   has a bad face index, 1 if it overflows the grid, 0.  `stages` = ofx_simplify_stages() runs everything; a smaller
+ *   value stops after that many of {keys, vertex sort, incidence sort, solve, face pass} (for timing the split; the
+ *   counts are then incomplete).
+ * ofx_simplify_extract: after the caller has read counts back, writes shape b's kept cluster positions (rounded once
+ *   to fp32, in ascending (ix, iy, iz) cell order) at out_verts + 3 * new_vert_off[b] and its kept faces (input order,
+ *   rotated so that the lowest cluster comes first, renumbered) at out_faces + 3 * new_tri_off[b]. */
+int ofx_simplify_stages(void);
+size_t ofx_simplify_ws_bytes(int64_t total_verts, int64_t total_faces, int batch);
+int ofx_simplify_cluster(const float* verts, const int32_t* faces, const int64_t* vert_off, const int64_t* tri_off,
+                         int batch, int64_t total_verts, int64_t total_faces, int cells, double cell_size, double reg,
+                         int stages, int64_t* counts, void* ws, int32_t* status, void* stream);
+int ofx_simplify_extract(const int32_t* faces, const int64_t* vert_off, const int64_t* tri_off, int batch,
+                         int64_t total_verts, int64_t total_faces, const int64_t* new_vert_off,
+                         const int64_t* new_tri_off, float* out_verts, int32_t* out_faces, void* ws,
+                         const int32_t* status, void* stream);
+
 /* ------------------------------------------------------------------ voxel meshes of octrees (csrc/ofx_voxmesh.hip)
  * The octree export of the generate path (export_octree, octfusion_model_union.py:403-422: the nodes of one depth
  * scattered into a dense float grid, then voxel2mesh / _voxel2mesh, ldm_diffusion_util.py:345-446, a Python loop over

@@ -179,6 +179,10 @@ _SIGS = {
     'ofx_mesh_cc_stats': (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_l, c_l, c_l, c_p, c_p, c_p, c_p], True),
     'ofx_mesh_cc_select': (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_l, c_l, c_p, c_p, c_p, c_p, c_p], True),
     'ofx_mesh_cc_extract': (c_i, [c_p, c_p, c_p, c_p, c_i, c_l, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_p], True),
+    'ofx_simplify_stages': (c_i, [], False),
+    'ofx_simplify_ws_bytes': (c_sz, [c_l, c_l, c_i], False),
+    'ofx_simplify_cluster': (c_i, [c_p, c_p, c_p, c_p, c_i, c_l, c_l, c_i, c_d, c_d, c_i, c_p, c_p, c_p, c_p], True),
+    'ofx_simplify_extract': (c_i, [c_p, c_p, c_p, c_i, c_l, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_p], True),
     'ofx_voxmesh_ws_bytes': (c_sz, [c_i, c_i, c_i], False),
     'ofx_voxmesh_mask_keys': (c_i, [c_p, c_l, c_i, c_i, c_i, c_p, c_p], True),
     'ofx_voxmesh_mask_dense': (c_i, [c_p, c_i, c_i, c_f, c_p, c_p], True),

@@ -19,6 +19,7 @@ mesh.py lists the differences).
     python -m octfusion_amd.generate --config snet_uncond --shapes 8 --mesh --points 2048 --out samples  # + <i>.npy
     python -m octfusion_amd.generate --config snet_uncond --shapes 8 --mesh --clean --out samples   # largest component
     python -m octfusion_amd.generate --config snet_uncond --shapes 8 --mesh --views --out samples   # + fid_images/
+    python -m octfusion_amd.generate --config snet_uncond --shapes 8 --mesh --simplify 64 --out samples  # small .obj
     python -m octfusion_amd.generate --config snet_uncond --shapes 8 --no-vae --octree-mesh --out samples
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \\
         -m octfusion_amd.generate --config snet_cond --shapes 32 --category 2
@@ -82,7 +83,7 @@ def prepare(config, rank, device, ckpt=None, vae_ckpt=None, with_vae=True, allow
 def generate(net, cfg, n_shapes, rank, world, seed=0, ddim_steps=200, label=None, vae=None, out_dir=None,
              shapes_per_call=1, use_graph=None, sdf_resolution=None, timings=None, mesh=False, mesh_level=0.0,
              mesh_scale=1.0, points=None, mesh_clean=False, octree_mesh=False, views=False, view_size=299,
-             view_samples=1):
+             view_samples=1, mesh_simplify=None):
     """Yields (result indices, output dict, seconds) for every group of shapes this rank owns.  mesh: also
     out['meshes'] (needs the VAE and sdf_resolution), written as <out_dir>/<index>.obj.  points (needs mesh): also
     out['points'] = {position in the group: [points, 3] cloud} of every non-empty mesh, sampled on the device after the
@@ -93,11 +94,16 @@ def generate(net, cfg, n_shapes, rank, world, seed=0, ddim_steps=200, label=None
     views (needs mesh): also out['views'] = {position in the group: uint8 [20, view_size, view_size, 3]}, every
     non-empty mesh (the cleaned one under mesh_clean) seen from the 20 FID views (render.render, view_samples samples
     per pixel), written as
-    <out_dir>/fid_images/view_<j>/<index>.png -- the layout of the reference's generate_synth_image.py."""
+    <out_dir>/fid_images/view_<j>/<index>.png -- the layout of the reference's generate_synth_image.py.
+    mesh_simplify=N (needs mesh): also out['simple_meshes'], every mesh (the cleaned one under mesh_clean) simplified
+    by vertex clustering with N cells along its longest side (simplify.simplify), and <out_dir>/<index>.obj is that
+    mesh; out['meshes'], the clouds and the views stay those of the full mesh."""
     if mesh_clean and not mesh:
         raise ValueError('mesh_clean needs mesh')
     if views and not mesh:
         raise ValueError('views needs mesh')
+    if mesh_simplify is not None and not mesh:
+        raise ValueError('mesh_simplify needs mesh')
     cs = CascadeSampler(net, cfg, vae)
     dev = cs.device
     for idxs in plan(n_shapes, rank, world, shapes_per_call):
@@ -121,6 +127,9 @@ def generate(net, cfg, n_shapes, rank, world, seed=0, ddim_steps=200, label=None
             out['points'] = sample_points(out['meshes'], idxs, points, seed)
         if views:
             out['views'] = render_views(out['meshes'], view_size, view_samples)
+        if mesh_simplify is not None:
+            from . import simplify
+            out['simple_meshes'] = simplify.simplify(out['meshes'], cells=mesh_simplify)
         if out_dir is not None:
             write_outputs(out_dir, idxs, out, cfg)
         yield idxs, out, dt
@@ -151,7 +160,8 @@ def render_views(meshes, size=299, samples=1):
 def write_outputs(out_dir, idxs, out, cfg):
     """Per shape: <index>/split_small.pth (+ split_large.pth) in the reference's sample-file format
     (tools/gen_split.py:50-54), <index>/sdf.pt when the SDF lattice was computed, and <index>.obj (export_mesh's
-    file name, octfusion_model_union.py:466) when the meshes were -- an empty mesh is skipped with a warning -- and
+    file name, octfusion_model_union.py:466) when the meshes were -- the simplified mesh when there is one; an empty
+    mesh is skipped with a warning -- and
     <index>.npy, its [points, 3] surface samples, when they were.  With the octree meshes: octree/<index>.obj
     (export_octree's file name, :376,420) and, for the large depth, octree_large/<index>.obj -- the reference writes
     both depths to octree/<index>.obj, so its depth-8 file replaces the depth-6 one
@@ -175,7 +185,7 @@ def write_outputs(out_dir, idxs, out, cfg):
             torch.save(out['sdfs'][b].cpu(), os.path.join(d, 'sdf.pt'))
         if 'meshes' in out:
             from . import mesh
-            mesh.write_obj(os.path.join(out_dir, '%d.obj' % i), *out['meshes'][b])
+            mesh.write_obj(os.path.join(out_dir, '%d.obj' % i), *out.get('simple_meshes', out['meshes'])[b])
         for key, sub in (('octree_meshes', 'octree'), ('octree_meshes_large', 'octree_large')):
             if key in out:
                 from . import mesh
@@ -205,15 +215,21 @@ def run(args, rank, local_rank, world, device):
     clean = getattr(args, 'clean', False)
     if clean and not mesh:
         raise ValueError('--clean needs --mesh')
+    simple = getattr(args, 'simplify', None)
+    if simple is not None and not mesh:
+        raise ValueError('--simplify needs --mesh')
     per_rank = len(dist.shard_indices(args.shapes, rank, world))
     batch = args.batch or max(1, min(8, per_rank))
     timings = {}
     done = []
     mesh_counts = {}
     mesh_comps = {}
+    simple_counts = {}
     kw = dict(mesh=True, mesh_level=args.mesh_level, mesh_scale=mesh_scale(args.config), points=points) if mesh else {}
     if clean:
         kw['mesh_clean'] = True
+    if simple is not None:
+        kw['mesh_simplify'] = simple
     if getattr(args, 'views', False):
         if not mesh or not args.out:
             raise ValueError('--views needs --mesh and --out')
@@ -231,6 +247,8 @@ def run(args, rank, local_rank, world, device):
             mesh_counts[i] = (int(v.shape[0]), int(f.shape[0]))
         for i, k in zip(idxs, out.get('mesh_components', ())):
             mesh_comps[i] = int(k)
+        for i, (v, f) in zip(idxs, out.get('simple_meshes', ())):
+            simple_counts[i] = (int(v.shape[0]), int(f.shape[0]))
     total = sum(dt for _, dt in done)
     tmax = dist.max_over_ranks(total, device)
     res = {'config': args.config, 'shapes': args.shapes, 'world': world, 'steps_per_stage': args.steps,
@@ -243,6 +261,9 @@ def run(args, rank, local_rank, world, device):
         res['rank0_mesh_faces'] = [mesh_counts[i][1] for i in res['rank0_indices']]
     if clean:
         res['rank0_mesh_components'] = [mesh_comps[i] for i in res['rank0_indices']]
+    if simple is not None:
+        res['rank0_simple_vertices'] = [simple_counts[i][0] for i in res['rank0_indices']]
+        res['rank0_simple_faces'] = [simple_counts[i][1] for i in res['rank0_indices']]
     return res
 
 
@@ -271,6 +292,10 @@ def main(argv=None):
                     help='with --mesh: keep only the largest connected component of every mesh (the reference\'s '
                          'export_mesh clean=True); the .obj, the --points cloud and the vertex / face counts are the '
                          'cleaned mesh\'s, and the result line gains rank0_mesh_components (counts before cleaning)')
+    ap.add_argument('--simplify', type=int, default=None, metavar='N',
+                    help='with --mesh: write <out>/<index>.obj simplified by vertex clustering on the device, N cells '
+                         '(1 .. 1024) along the longest side of every mesh (the cleaned one under --clean); --points and '
+                         '--views keep the full mesh, and the result line gains rank0_simple_vertices / _faces')
     ap.add_argument('--octree-mesh', action='store_true',
                     help='write the generated octree itself as a mesh of cubes, <out>/octree/<index>.obj (the '
                          'reference\'s export_octree) and, for a three-stage config, <out>/octree_large/<index>.obj; '
@@ -285,6 +310,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.clean and not args.mesh:
         raise ValueError('--clean needs --mesh')
+    if args.simplify is not None and not args.mesh:
+        raise ValueError('--simplify needs --mesh')
     if args.views and not (args.mesh and args.out):
         raise ValueError('--views needs --mesh and --out')
     if args.octree_mesh and not args.out:
