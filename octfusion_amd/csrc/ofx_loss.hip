@@ -32,16 +32,19 @@ __global__ void __launch_bounds__(256) octree_ce_kernel(const float* __restrict_
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     const float l0 = logits[i * ld], l1 = logits[i * ld + 1];
     const int label = child[i] >= 0 ? 1 : 0;                       // nempty_mask(d) (loss.py:117)
-    const float m = fmaxf(l0, l1);
-    const float e0 = expf(l0 - m), e1 = expf(l1 - m);
-    const float lse = m + logf(e0 + e1);
-    loss += (double)(lse - (label ? l1 : l0));
+    // the softplus of d = l_other - l_label: two non-negative terms.  m + logf(e0 + e1) - l_label rounds 1 + exp(-margin)
+    // to 1 and m + tiny to m once the labelled logit leads by a few units -- most rows of a trained split classifier --
+    // and e * inv - 1 loses the gradient of the labelled logit the same way.
+    const float d = label ? l0 - l1 : l1 - l0;
+    const float e = expf(-fabsf(d));
+    loss += (double)(fmaxf(d, 0.f) + log1pf(e));
     const int arg = l1 > l0 ? 1 : 0;                               // argmax returns the first maximum
     hit += arg == label ? 1.0 : 0.0;
     if (dlogits) {
-      const float inv = 1.0f / (e0 + e1);
-      dlogits[i * ldd] = (e0 * inv - (label ? 0.f : 1.f)) * dscale;
-      dlogits[i * ldd + 1] = (e1 * inv - (label ? 1.f : 0.f)) * dscale;
+      const float inv = 1.0f / (1.0f + e);
+      const float g = (d >= 0.f ? inv : e * inv) * dscale;         // sigmoid(d): + to the other class, - to the label
+      dlogits[i * ldd + (label ? 0 : 1)] = g;
+      dlogits[i * ldd + (label ? 1 : 0)] = -g;
     }
   }
   const double s0 = block_sum(loss, red);

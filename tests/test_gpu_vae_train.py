@@ -110,7 +110,9 @@ def test_mpu_gradient_and_adjoint_vs_oracle(golden):
 
 def test_loss_kernels_vs_oracle():
     """ofx_octree_ce / ofx_sdf_reg_loss / ofx_kl_sample_* against torch (F.cross_entropy, the formulas of
-    loss.py:23-29, distributions.py:24-46) incl. ties, huge logits, clamped log-variances and empty inputs."""
+    loss.py:23-29, distributions.py:24-46) incl. ties, huge logits, clamped log-variances and empty inputs.  One size,
+    tight pitches, through the Python wrappers: the entry points themselves -- every size class, pitch, NULL output,
+    refusal and the `sums +=` contract, against float64 with derived bounds -- are tests/test_gpu_loss_entry.py's."""
     import torch.nn.functional as F
     from oracle import loss as OL
     from octfusion_amd import vae_training as VT
