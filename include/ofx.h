@@ -494,7 +494,15 @@ int ofx_graphconv_narrow_out(const float* P, int64_t ldp, int cout, int64_t n_no
  *      rows zero-padded to a whole tile; ofx_planes_packed_bytes() bytes.
  * ofx_graphconv_fwd_planes: as ofx_graphconv_fwd, with xp / aux / tfp planes (row pitches in BYTES, 128-B
  *      aligned bases and pitches), aux = scratch of aux_bytes >= (n_multi + 1) * ldx_bytes, tfp = planes of the
- *      type_frac slab padded to a whole chunk (NULL when nt <= 1), W2 = packed planes weights.
+ *      type_frac slab padded to a whole chunk (NULL when nt <= 1; ldt_bytes >= 128 * ceil(7 nt / chunk), chunk = 32
+ *      channels in modes 2 / 3 and 64 in mode 1, else OFX_EINVAL), W2 = packed planes weights.
+ *      Any cout >= 1 and any 4-B aligned out / res / emb / bias with pitches >= cout are accepted; the float4 epilogue
+ *      (and with it the persistent launch and the two-stage statistics) needs cout % 4 == 0, 16-B aligned out / res /
+ *      emb / bias and ldc, ldr, lde % 4 == 0, everything else takes a scalar epilogue with fp64-atomic statistics.
+ *      The launches read nothing outside the operands: rows [0, n_nodes) x cout floats of res at pitch ldr, cout floats
+ *      of bias and of every emb row that batch_id names, n_nodes batch ids, the plane lines of xp / aux / tfp and the
+ *      packed weights with their trailer; no readable slack is required behind any of them (nbr_ext under the
+ *      persistent launch excepted, below).
  *      Two launch shapes (csrc/ofx_gemm3.hip, csrc/ofx_gemm2.hip):
  *      - persistent stream-K blocks (default when `sync` is given and the layer has >= 64 k-step units): as many
  *        blocks as the device holds at once, each owning an equal contiguous share of the (tile, k-step) sequence;

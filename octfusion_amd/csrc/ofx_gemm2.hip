@@ -329,6 +329,9 @@ __global__ void __launch_bounds__(512, 2) gconv2_kernel(const Gemm2Args a) {   /
   // the last k-steps; its barrier lets those (and, with 3 stages, the 6 new DMA) stay outstanding.
   G2Epi<G2_MI, G2_NI> P;
   const bool vec4 = g.vec4 != 0;
+  // (the request phase below is told `g.vec4 != 0` afresh: handing it this local instead re-allocates the scalar registers
+  // of the whole kernel -- 18 fewer SGPRs, 52 fewer instructions in the NI = 2 instantiations -- which is a change to
+  // measure, not one to slip in with a bounds fix; as written every instantiation differs by 4-5 instructions)
   auto step_issue = [&](const Tile& T, auto last_tag) {
     constexpr bool LAST = decltype(last_tag)::value;
     if constexpr (CF::NBUF == 3) {
@@ -338,7 +341,7 @@ __global__ void __launch_bounds__(512, 2) gconv2_kernel(const Gemm2Args a) {   /
       g2_wait_lgkm<4, PREC>(F0);
       G2_FENCE();
       if (LAST) {
-        g2_epilogue_request<G2_WM, G2_WN, G2_MI, G2_NI>(g, (const void*)a.W2, P, m0, n0, wm, wn, l31, h);
+        g2_epilogue_request<G2_WM, G2_WN, G2_MI, G2_NI>(g, (const void*)a.W2, P, m0, n0, wm, wn, l31, h, -1, g.vec4 != 0);
         G2_FENCE();
       }
       mfma_spliced(F0, true, ob, 1, F1, std::true_type(), T, obnn);
@@ -352,7 +355,7 @@ __global__ void __launch_bounds__(512, 2) gconv2_kernel(const Gemm2Args a) {   /
       g2_wait_lgkm<0, PREC>(F0);
       G2_FENCE();
       if (LAST) {
-        g2_epilogue_request<G2_WM, G2_WN, G2_MI, G2_NI>(g, (const void*)a.W2, P, m0, n0, wm, wn, l31, h);
+        g2_epilogue_request<G2_WM, G2_WN, G2_MI, G2_NI>(g, (const void*)a.W2, P, m0, n0, wm, wn, l31, h, -1, g.vec4 != 0);
         G2_FENCE();
       }
       mfma_spliced(F0, true, ob, 1, F1, std::false_type(), T, 0);
@@ -702,7 +705,10 @@ extern "C" int ofx_graphconv_fwd_planes_cus(const void* xp, int64_t ldx_bytes, i
     return OFX_EINVAL;
   if (aux_bytes < (size_t)(n_multi + 1) * (size_t)ldx_bytes) return OFX_EINVAL;      // aux rows are written / gathered at the pitch of xp
   const int ntc = nt > 1 ? nt : 0;
-  if (ntc > 0 && (!tfp || (ldt_bytes & 127) || ((uintptr_t)tfp & 127))) return OFX_EINVAL;
+  // (the type slab is read as whole 128-B lines: ceil(7 nt / chunk) of them per row)
+  if (ntc > 0 && (!tfp || (ldt_bytes & 127) || ((uintptr_t)tfp & 127) ||
+                  ldt_bytes < (7 * (int64_t)ntc + ch - 1) / ch * G2_LINE))
+    return OFX_EINVAL;
   if (stats && (!batch_id || stats_ld < cout)) return OFX_EINVAL;
   hipStream_t st = ofx_stream(stream);
   if (!aux_ready)         // the producer of xp (ofx_gn_apply_planes / ofx_planes_split) may have written aux already

@@ -201,10 +201,15 @@ template <int NI> constexpr int g2_epi_slice_loads(int slice) { return slice == 
 template <int WM, int WN, int MI, int NI, int SLICE>
 __device__ __forceinline__ void g2_epilogue_request_slice(const GemmArgs& g, const void* dummy, G2Epi<MI, NI>& P,
                                                           int64_t m0, int64_t n0, int wm, int wn, int l31, int h,
-                                                          int b0w = -1) {
+                                                          int b0w = -1, bool v4 = true) {
   const int q = l31 & 3, k = l31 >> 2;
   const int64_t mw = m0 + wm * MI * 32;
   const int64_t mlast = g.M - 1;
+  // v4: the float4 epilogue will consume what is requested here (always, in the persistent kernel).  Only its argument
+  // sets (N % 4 == 0, hence N >= 4) make a 16-B piece at a clamped column lie inside its row.  The scalar epilogue of
+  // gconv2_kernel loads its own operands element by element: for it (v4 false) every request reads the dummy line, so
+  // that nothing outside bias / emb / res is touched when cout % 4 != 0 (a piece would run up to 12 B past the row end)
+  // or cout < 4 (N - 4 is negative).
   if constexpr (SLICE == 0) {
     const bool need_bid = g.emb || g.stats;
     {
@@ -220,8 +225,8 @@ __device__ __forceinline__ void g2_epilogue_request_slice(const GemmArgs& g, con
       // wave's FIRST row's batch element -- the row a wave that lies inside one batch element adds to every output
       // (g2_epilogue_finish checks that); the finish phase then has no load of its own to wait for
       const void* bp = dummy;
-      if (g.bias) bp = g.bias + n;
-      else if (g.emb && b0w >= 0) bp = g.emb + (int64_t)b0w * g.lde + n;
+      if (g.bias && v4) bp = g.bias + n;
+      else if (g.emb && b0w >= 0 && v4) bp = g.emb + (int64_t)b0w * g.lde + n;
       g2_req128(P.bias[j], bp);
     }
   } else {
@@ -232,15 +237,16 @@ __device__ __forceinline__ void g2_epilogue_request_slice(const GemmArgs& g, con
     for (int G = 0; G < 4; ++G) {
       int64_t m = mw + i * 32 + q + 4 * h + 8 * G;
       m = m < mlast ? m : mlast;
-      g2_req128(P.res[i][j][G], g.res ? (const void*)(g.res + m * g.ldr + n) : dummy);
+      g2_req128(P.res[i][j][G], g.res && v4 ? (const void*)(g.res + m * g.ldr + n) : dummy);
     }
   }
 }
 template <int WM, int WN, int MI, int NI>
 __device__ __forceinline__ void g2_epilogue_request(const GemmArgs& g, const void* dummy, G2Epi<MI, NI>& P, int64_t m0,
-                                                    int64_t n0, int wm, int wn, int l31, int h, int b0w = -1) {
+                                                    int64_t n0, int wm, int wn, int l31, int h, int b0w = -1,
+                                                    bool v4 = true) {
   g2_static_for<1 + MI * NI>([&](auto s_tag) {
-    g2_epilogue_request_slice<WM, WN, MI, NI, decltype(s_tag)::value>(g, dummy, P, m0, n0, wm, wn, l31, h, b0w);
+    g2_epilogue_request_slice<WM, WN, MI, NI, decltype(s_tag)::value>(g, dummy, P, m0, n0, wm, wn, l31, h, b0w, v4);
   });
 }
 // after the vmcnt(0) of the last k-steps: ties every requested register to this point of the instruction stream
