@@ -409,7 +409,8 @@ int ofx_gemm_f32_planes(const float* A, int64_t lda, const int32_t* a_rows, int6
  * reference's per-batch-element time-embedding add (modules.py:754-758), res
  * the residual / skip add (:763).  type_frac may be NULL (nt <= 1).
  * nbr = ofx_graph_primary table (col path: any cin).  nbr_ext / multi_seg / aux
- * (scratch of (n_multi+1)*cin floats) enable the branch-free fast path when
+ * (scratch of (n_multi+1)*ldx floats: aux rows have the row pitch of x, of which the
+ * first cin floats are written) enable the branch-free fast path when
  * cin % 32 == 0: a pre-pass averages the few multi-neighbour segments into aux, the
  * main kernel then gathers exactly one row per (row,dir).  ws: split-K workspace.
  * Col path (no nbr_ext, cin % 32 != 0, or x / ldx / aux not 16-B aligned): col_data rows
