@@ -785,6 +785,44 @@ int ofx_mc_emit(const float* sdf, int batch, int size, float level, float step, 
                 const int64_t* vert_off, const int64_t* tri_off, float* verts, int32_t* faces, void* stream);
 int ofx_mc_table_host(int8_t* tri_table, uint8_t* ntri);
 
+/* ------------------------------------------------------------------ field meshing (csrc/ofx_fieldmesh.hip)
+ * Marching cubes of the NeuralMPU field without a dense lattice (2 <= size <= 2048).  The lattice is
+ * ofx_mpu_eval_grid's: coordinate fl(fl(i * step) + bbmin), SDF bit-equal to what that sweep writes.  It is cut into
+ * bricks of 8^3 cells, nb = ceil((size - 1) / 8) per axis, brick (I, J, K) = linear index (I * nb + J) * nb + K; a
+ * brick owns the cells [8I, min(8I + 8, size - 1)) per axis and holds the points [8I, min(8I + 8, size - 1)] (its
+ * frame).  Per axis lo = cell(c(first point)), hi = cell(c(last point)), cell(c) = floor((c + 1) * 2^(de-1)) in fp32;
+ * the brick is ACTIVE iff the box [lo - margin, hi + margin], clipped to [0, 2^de - 1], holds a node of the shape at
+ * depth de = depth_end (empty or not); every brick is active when de <= full_depth.  The mesh is ofx_mc_emit's (same
+ * inside test, interpolation, mapping, table and winding) restricted to the cells of active bricks: one vertex per
+ * crossing lattice edge held by an active brick's frame, written by the lowest-indexed active brick that holds it,
+ * ordered by (rank of that brick among the shape's active bricks, owner point (lx * 9 + ly) * 9 + lz in its frame,
+ * axis); triangles ordered by (rank of the brick, cell (cx * 8 + cy) * 8 + cz, table order).  Scans only: bitwise
+ * reproducible, and a shape's result does not depend on the other shapes of the call.
+ * Shapes batch0 .. batch0 + batch - 1 of the tree are meshed; 1 <= batch <= 128.
+ * ofx_fieldmesh_classify: fills cws (>= ofx_fieldmesh_classify_ws_bytes(batch, size) bytes, 16-byte aligned);
+ *   counts[b*2 + {0,1}] = active bricks, bricks active at margin 0 ("seeds") of shape b (int64, device).
+ * ofx_fieldmesh_count: n_bricks = the sum of the active-brick counts the caller read back, 1 <= n_bricks <= 2^26;
+ *   ws >= ofx_fieldmesh_ws_bytes(n_bricks) bytes (4404 B per brick: its 729 samples, a 16-bit id map, list, counts,
+ *   scans), 16-byte aligned; code as for ofx_mpu_eval_grid.
+ *   counts[b*4 + {0,1,2,3}] = vertices, triangles, cells with a non-finite corner, leaks of shape b (int64, device),
+ *   summed in int64.  The emit pass scans the call's vertex and triangle counts in int32: the caller must not call
+ *   ofx_fieldmesh_emit unless the vertices of all shapes of the call together, and the triangles, are <= INT32_MAX.
+ *   A leak is a crossing lattice edge that lies in a face shared by an active and an inactive brick.
+ * ofx_fieldmesh_emit: after the caller has read the counts back, writes shape b's vertices at verts + 3 * vert_off[b]
+ *   and its triangles at faces + 3 * tri_off[b] (offsets: int64 device arrays), from the same cws / ws.
+ * OFX_EINVAL with nothing launched for a size, batch, depth, margin < 0, non-finite level / step / bbmin, step <= 0,
+ * NULL or mis-aligned pointer outside the above; the ws_bytes functions return 0 there. */
+size_t ofx_fieldmesh_classify_ws_bytes(int batch, int size);
+size_t ofx_fieldmesh_ws_bytes(int64_t n_bricks);
+int ofx_fieldmesh_classify(const ofx_tree_t* tree, int depth_end, int batch0, int batch, int size, float step,
+                           float bbmin, int margin, void* cws, int64_t* counts, void* stream);
+int ofx_fieldmesh_count(const ofx_tree_t* tree, int depth_start, int depth_end, const float* code, int batch0,
+                        int batch, int size, float step, float bbmin, float level, const void* cws, int64_t n_bricks,
+                        void* ws, int64_t* counts, void* stream);
+int ofx_fieldmesh_emit(int batch, int size, float level, float step, float bbmin, float scale, const void* cws,
+                       int64_t n_bricks, void* ws, const int64_t* vert_off, const int64_t* tri_off, float* verts,
+                       int32_t* faces, void* stream);
+
 /* ------------------------------------------------------------------ mesh components (csrc/ofx_mesh_cc.hip)
  * export_mesh's clean=True (models/octfusion_model_union.py:459-467; the same code in octfusion_model_vae.py:242-250):
  * trimesh.split(only_watertight=False), keep the component whose bounding box has the largest side.

@@ -173,6 +173,12 @@ _SIGS = {
     'ofx_mc_count': (c_i, [c_p, c_i, c_i, c_f, c_p, c_p, c_p], True),
     'ofx_mc_emit': (c_i, [c_p, c_i, c_i, c_f, c_f, c_f, c_f, c_p, c_p, c_p, c_p, c_p, c_p], True),
     'ofx_mc_table_host': (c_i, [c_p, c_p], True),
+    'ofx_fieldmesh_classify_ws_bytes': (c_sz, [c_i, c_i], False),
+    'ofx_fieldmesh_ws_bytes': (c_sz, [c_l], False),
+    'ofx_fieldmesh_classify': (c_i, [ctypes.POINTER(OfxTree), c_i, c_i, c_i, c_i, c_f, c_f, c_i, c_p, c_p, c_p], True),
+    'ofx_fieldmesh_count': (c_i, [ctypes.POINTER(OfxTree), c_i, c_i, c_p, c_i, c_i, c_i, c_f, c_f, c_f, c_p, c_l, c_p,
+                                  c_p, c_p], True),
+    'ofx_fieldmesh_emit': (c_i, [c_i, c_i, c_f, c_f, c_f, c_f, c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_p], True),
     'ofx_mesh_cc_ws_bytes': (c_sz, [c_l, c_l, c_i], False),
     'ofx_mesh_cc_label': (c_i, [c_p, c_p, c_p, c_i, c_l, c_l, c_p, c_p, c_p, c_p], True),
     'ofx_mesh_cc_table': (c_i, [c_p, c_p, c_p, c_p, c_i, c_l, c_l, c_p, c_p, c_p, c_p, c_p], True),

@@ -83,7 +83,7 @@ def prepare(config, rank, device, ckpt=None, vae_ckpt=None, with_vae=True, allow
 def generate(net, cfg, n_shapes, rank, world, seed=0, ddim_steps=200, label=None, vae=None, out_dir=None,
              shapes_per_call=1, use_graph=None, sdf_resolution=None, timings=None, mesh=False, mesh_level=0.0,
              mesh_scale=1.0, points=None, mesh_clean=False, octree_mesh=False, views=False, view_size=299,
-             view_samples=1, mesh_simplify=None):
+             view_samples=1, mesh_simplify=None, field_mesh=False, mesh_margin=1):
     """Yields (result indices, output dict, seconds) for every group of shapes this rank owns.  mesh: also
     out['meshes'] (needs the VAE and sdf_resolution), written as <out_dir>/<index>.obj.  points (needs mesh): also
     out['points'] = {position in the group: [points, 3] cloud} of every non-empty mesh, sampled on the device after the
@@ -97,7 +97,12 @@ def generate(net, cfg, n_shapes, rank, world, seed=0, ddim_steps=200, label=None
     <out_dir>/fid_images/view_<j>/<index>.png -- the layout of the reference's generate_synth_image.py.
     mesh_simplify=N (needs mesh): also out['simple_meshes'], every mesh (the cleaned one under mesh_clean) simplified
     by vertex clustering with N cells along its longest side (simplify.simplify), and <out_dir>/<index>.obj is that
-    mesh; out['meshes'], the clouds and the views stay those of the full mesh."""
+    mesh; out['meshes'], the clouds and the views stay those of the full mesh.
+    field_mesh (needs mesh): the meshes come from mesh.field_mesh (octree-guided bricks, sdf_resolution up to 2048,
+    mesh_margin finest octree cells around the finest nodes) instead of the dense sweep: out['mesh_stats'] holds the
+    per-shape seeds / bricks / leaks / total_bricks, and there is no out['sdfs'], hence no sdf.pt."""
+    if field_mesh and not mesh:
+        raise ValueError('field_mesh needs mesh')
     if mesh_clean and not mesh:
         raise ValueError('mesh_clean needs mesh')
     if views and not mesh:
@@ -117,6 +122,7 @@ def generate(net, cfg, n_shapes, rank, world, seed=0, ddim_steps=200, label=None
                         use_graph=use_graph, sdf_resolution=sdf_resolution if vae is not None else None,
                         timings=timings, mesh=mesh, mesh_level=mesh_level, mesh_scale=mesh_scale,
                         **({'mesh_clean': True} if mesh_clean else {}),
+                        **({'field_mesh': True, 'mesh_margin': mesh_margin} if field_mesh else {}),
                         **({'octree_mesh': True} if octree_mesh else {}))
         if dev.type == 'cuda':
             torch.cuda.synchronize()
@@ -218,18 +224,29 @@ def run(args, rank, local_rank, world, device):
     simple = getattr(args, 'simplify', None)
     if simple is not None and not mesh:
         raise ValueError('--simplify needs --mesh')
+    field = getattr(args, 'field_mesh', False)
+    if field:
+        from .mesh import FIELD_MAX_SIZE
+        if not mesh:
+            raise ValueError('--field-mesh needs --mesh')
+        if not 2 <= args.sdf_resolution <= FIELD_MAX_SIZE or getattr(args, 'mesh_margin', 1) < 0:
+            raise ValueError('--field-mesh needs 2 <= --sdf-resolution <= %d and --mesh-margin >= 0' % FIELD_MAX_SIZE)
     per_rank = len(dist.shard_indices(args.shapes, rank, world))
     batch = args.batch or max(1, min(8, per_rank))
     timings = {}
     done = []
     mesh_counts = {}
     mesh_comps = {}
+    mesh_stats = {}
     simple_counts = {}
     kw = dict(mesh=True, mesh_level=args.mesh_level, mesh_scale=mesh_scale(args.config), points=points) if mesh else {}
     if clean:
         kw['mesh_clean'] = True
     if simple is not None:
         kw['mesh_simplify'] = simple
+    if field:
+        kw['field_mesh'] = True
+        kw['mesh_margin'] = getattr(args, 'mesh_margin', 1)
     if getattr(args, 'views', False):
         if not mesh or not args.out:
             raise ValueError('--views needs --mesh and --out')
@@ -249,6 +266,8 @@ def run(args, rank, local_rank, world, device):
             mesh_comps[i] = int(k)
         for i, (v, f) in zip(idxs, out.get('simple_meshes', ())):
             simple_counts[i] = (int(v.shape[0]), int(f.shape[0]))
+        for b, i in enumerate(idxs if 'mesh_stats' in out else ()):
+            mesh_stats[i] = {k: int(v[b]) for k, v in out['mesh_stats'].items()}
     total = sum(dt for _, dt in done)
     tmax = dist.max_over_ranks(total, device)
     res = {'config': args.config, 'shapes': args.shapes, 'world': world, 'steps_per_stage': args.steps,
@@ -261,6 +280,10 @@ def run(args, rank, local_rank, world, device):
         res['rank0_mesh_faces'] = [mesh_counts[i][1] for i in res['rank0_indices']]
     if clean:
         res['rank0_mesh_components'] = [mesh_comps[i] for i in res['rank0_indices']]
+    if field:
+        res['mesh_margin'] = kw['mesh_margin']
+        for k in ('seeds', 'bricks', 'leaks', 'total_bricks'):
+            res['rank0_mesh_' + k] = [mesh_stats[i][k] for i in res['rank0_indices']]
     if simple is not None:
         res['rank0_simple_vertices'] = [simple_counts[i][0] for i in res['rank0_indices']]
         res['rank0_simple_faces'] = [simple_counts[i][1] for i in res['rank0_indices']]
@@ -292,6 +315,13 @@ def main(argv=None):
                     help='with --mesh: keep only the largest connected component of every mesh (the reference\'s '
                          'export_mesh clean=True); the .obj, the --points cloud and the vertex / face counts are the '
                          'cleaned mesh\'s, and the result line gains rank0_mesh_components (counts before cleaning)')
+    ap.add_argument('--field-mesh', action='store_true',
+                    help='with --mesh: mesh the decoded field in octree-guided 8^3-cell bricks instead of sweeping the '
+                         'lattice (mesh.field_mesh): --sdf-resolution may go up to 2048, no sdf.pt is written, and the '
+                         'result line gains rank0_mesh_seeds / _bricks / _leaks / _total_bricks.  Surface sheets '
+                         'inside coarse leaves, outside the band, are not meshed')
+    ap.add_argument('--mesh-margin', type=int, default=1, metavar='M',
+                    help='with --field-mesh: width of the band around the finest octree nodes, in finest-level cells')
     ap.add_argument('--simplify', type=int, default=None, metavar='N',
                     help='with --mesh: write <out>/<index>.obj simplified by vertex clustering on the device, N cells '
                          '(1 .. 1024) along the longest side of every mesh (the cleaned one under --clean); --points and '
@@ -312,6 +342,8 @@ def main(argv=None):
         raise ValueError('--clean needs --mesh')
     if args.simplify is not None and not args.mesh:
         raise ValueError('--simplify needs --mesh')
+    if args.field_mesh and not args.mesh:
+        raise ValueError('--field-mesh needs --mesh')
     if args.views and not (args.mesh and args.out):
         raise ValueError('--views needs --mesh and --out')
     if args.octree_mesh and not args.out:

@@ -14,6 +14,7 @@ Differences from the reference:
     (csrc/ofx_mesh_cc.hip: components, largest_component): connectivity is by shared vertex where trimesh uses edges
     shared by exactly two faces, extents are fp32, a tie goes to the lowest vertex id.
 """
+import ctypes
 import os
 import warnings
 
@@ -101,6 +102,161 @@ def _group(sdf, b0, R, level, step, bbmin, scale, comps=None):
               _lib.ptr(offs[1]), _lib.ptr(verts), _lib.ptr(faces), st)
     if comps is not None:                              # clean=True: the batch buffers go on as they are
         return _clean(verts, faces, nv.tolist(), nt.tolist(), comps)
+    return [(verts[int(voff[b]):int(voff[b] + nv[b])], faces[int(toff[b]):int(toff[b] + nt[b])]) for b in range(B)]
+
+
+# ---- field meshing (csrc/ofx_fieldmesh.hip): marching cubes without the dense lattice --------------------------------
+FIELD_MAX_SIZE = 2048
+FIELD_MAX_BATCH = 128                          # shapes per call of the library
+FIELD_GROUP_BRICKS = 1 << 22                   # active bricks a call aims at (18 GB of workspace); one shape may pass
+FIELD_MAX_COUNT = 2 ** 31 - 1                  # vertices, and triangles, of one call: its emit pass scans them in int32
+FIELD_BRICK_BYTES = 4404                       # workspace per active brick: 729 samples, 16-bit id map, counts, scans
+
+
+def field_mesh(field, size, level=0.0, bbmin=-0.9, bbmax=0.9, scale=1.0, margin=1, clean=False, stats=None,
+               shapes=None):
+    """Meshes of the decoded NeuralMPU ``field`` (an ``mpu.MpuField``) on the ``size``^3 lattice of ``mpu.calc_sdf``,
+    2 <= size <= 2048, without ever holding that lattice: the field is evaluated only in bricks of 8^3 cells within
+    ``margin`` finest-level octree cells of a node at ``field.depth_out`` and meshed from there.  Returns what
+    ``marching_cubes(calc_sdf(field, ...))`` returns -- a list of ``(verts [V, 3] fp32, faces [F, 3] int32)`` device
+    tensors, one per shape, same coordinates, table and winding -- restricted to the cells of the active bricks;
+    sample values are bit-equal to the sweep's.  A surface sheet the field produces inside a coarse leaf, farther than
+    the margin from every finest node, is NOT meshed (the dense path finds it); ``leaks`` tells whether the surface
+    reached the edge of the band.  Vertices are ordered by (brick, point in the brick, axis), triangles by (brick, cell,
+    table order); the output is bitwise reproducible and a shape's mesh does not depend on the rest of the batch.
+
+    shapes: the batch indices to mesh (default: all), in the order of the result.  clean=True keeps each shape's
+    largest component.  stats (optional dict) gains ``seeds`` (bricks active at margin 0), ``bricks`` (active bricks),
+    ``leaks`` (crossing lattice edges on a face between an active and an inactive brick) and ``total_bricks`` (bricks
+    of the lattice), lists with one entry per meshed shape, and ``components`` with clean.
+
+    Two host synchronisations per group of shapes (the brick counts, then the vertex / triangle counts); device
+    memory is 4404 B per active brick plus the nb^3 brick flags and the output.  A shape is never cut: whatever number
+    of its bricks is active, up to all 2^24 of a 2048^3 lattice, goes through one call.  A batch is cut into groups of
+    consecutive shapes of about 4 M active bricks, and again if a group's vertices or triangles would pass 2^31 - 1.
+    Raises ValueError for a bad argument, for a shape whose active cells have a non-finite corner, and for a single
+    shape with more than 2^31 - 1 vertices or triangles (its faces are int32); OfxError without a GPU."""
+    from . import mpu
+    _lib.require_device()
+    if not isinstance(field, mpu.MpuField):
+        raise ValueError('field_mesh: field must be an mpu.MpuField')
+    size, margin = int(size), int(margin)
+    if not 2 <= size <= FIELD_MAX_SIZE:
+        raise ValueError('field_mesh: lattice size %d outside [2, %d]' % (size, FIELD_MAX_SIZE))
+    if not np.isfinite(level):
+        raise ValueError('field_mesh: level must be finite')
+    if margin < 0:
+        raise ValueError('field_mesh: margin must be >= 0')
+    if not (np.isfinite(bbmin) and np.isfinite(bbmax) and np.isfinite(scale) and bbmax > bbmin):
+        raise ValueError('field_mesh: needs finite bbmin < bbmax and a finite scale')
+    octree = field.octree
+    if not 0 <= field.full_depth <= field.depth_out <= octree.depth:
+        raise ValueError('field_mesh: depth_out %d outside [full_depth %d, octree depth %d]'
+                         % (field.depth_out, field.full_depth, octree.depth))
+    B = int(octree.batch_size)
+    shapes = list(range(B)) if shapes is None else [int(b) for b in shapes]
+    if any(not 0 <= b < B for b in shapes):
+        raise ValueError('field_mesh: shapes must lie in [0, %d)' % B)
+    h = mpu._TreeHandle.of(octree)
+    code = mpu._code(field.reg, h, field.full_depth, field.depth_out)
+    geo = (size, float(level), (float(bbmax) - float(bbmin)) / size, float(bbmin), float(scale), margin)
+    runs = []                                              # consecutive batch indices: one library call each
+    for b in shapes:
+        if runs and runs[-1][-1] + 1 == b and len(runs[-1]) < FIELD_MAX_BATCH:
+            runs[-1].append(b)
+        else:
+            runs.append([b])
+    out, acc = [], dict(seeds=[], bricks=[], leaks=[], components=[] if clean else None)
+    for run in runs:
+        out += _field_run(field, h, code, run[0], len(run), geo, acc)
+    if stats is not None:
+        stats.update(seeds=acc['seeds'], bricks=acc['bricks'], leaks=acc['leaks'],
+                     total_bricks=[(-(-(size - 1) // 8)) ** 3] * len(shapes))
+        if clean:
+            stats['components'] = acc['components']
+    return out
+
+
+def _field_classify(field, h, code, b0, B, geo):
+    """(classify workspace, [B, 2] host tensor of active bricks and seeds) of shapes b0 .. b0 + B - 1: host sync 1."""
+    size, level, step, bbmin, scale, margin = geo
+    cws = torch.empty(_lib.lib().ofx_fieldmesh_classify_ws_bytes(B, size), dtype=torch.uint8, device=code.device)
+    bc = torch.empty(B * 2, dtype=torch.int64, device=code.device)
+    _lib.call('ofx_fieldmesh_classify', ctypes.byref(h.tree), field.depth_out, b0, B, size, step, bbmin, margin,
+              _lib.ptr(cws), _lib.ptr(bc), _lib.stream())
+    return cws, bc.view(B, 2).cpu()
+
+
+def _field_run(field, h, code, b0, B, geo, acc):
+    """Consecutive shapes b0 .. b0 + B - 1: one group if their active bricks fit FIELD_GROUP_BRICKS, else groups of
+    consecutive shapes that do (a shape on its own may be larger), each classified once more on its own -- the ranks
+    a classify workspace holds are those of the shapes it was called for."""
+    cws, bc = _field_classify(field, h, code, b0, B, geo)
+    nb = bc[:, 0].tolist()
+    if B == 1 or sum(nb) <= FIELD_GROUP_BRICKS:
+        return _field_group(field, h, code, b0, B, geo, acc, cws, bc)
+    del cws
+    parts, cur = [[0, 0]], 0
+    for k in range(B):
+        if parts[-1][1] and cur + nb[k] > FIELD_GROUP_BRICKS:
+            parts.append([k, 0])
+            cur = 0
+        parts[-1][1] += 1
+        cur += nb[k]
+    out = []
+    for k, cnt in parts:
+        out += _field_group(field, h, code, b0 + k, cnt, geo, acc, *_field_classify(field, h, code, b0 + k, cnt, geo))
+    return out
+
+
+def _field_group(field, h, code, b0, B, geo, acc, cws, bc):
+    size, level, step, bbmin, scale, margin = geo
+    dev = code.device
+    st = _lib.stream()
+    L = _lib.lib()
+    tree = ctypes.byref(h.tree)
+    n = int(bc[:, 0].sum())
+    empty = (torch.empty(0, 3, dtype=torch.float32, device=dev), torch.empty(0, 3, dtype=torch.int32, device=dev))
+    if n == 0:
+        acc['bricks'] += bc[:, 0].tolist()
+        acc['seeds'] += bc[:, 1].tolist()
+        acc['leaks'] += [0] * B
+        if acc['components'] is not None:
+            acc['components'] += [0] * B
+        return [empty for _ in range(B)]
+    ws = torch.empty(L.ofx_fieldmesh_ws_bytes(n), dtype=torch.uint8, device=dev)
+    counts = torch.empty(B * 4, dtype=torch.int64, device=dev)
+    _lib.call('ofx_fieldmesh_count', tree, field.full_depth, field.depth_out, _lib.ptr(code), b0, B, size, step, bbmin,
+              level, _lib.ptr(cws), n, _lib.ptr(ws), _lib.ptr(counts), st)
+    c = counts.view(B, 4).cpu()                        # host sync 2
+    bad = torch.nonzero(c[:, 2]).flatten().tolist()
+    if bad:
+        raise ValueError('field_mesh: shape %d has %d cells with a non-finite corner'
+                         % (b0 + bad[0], int(c[bad[0], 2])))
+    nv, nt = c[:, 0], c[:, 1]
+    if max(int(nv.sum()), int(nt.sum())) > FIELD_MAX_COUNT:    # the emit pass scans a call's counts in int32
+        if B == 1:
+            raise ValueError('field_mesh: shape %d has %d vertices and %d triangles, more than %d'
+                             % (b0, int(nv[0]), int(nt[0]), FIELD_MAX_COUNT))
+        del ws, cws
+        out = []
+        for k, cnt in ((0, B // 2), (B // 2, B - B // 2)):
+            out += _field_group(field, h, code, b0 + k, cnt, geo, acc,
+                                *_field_classify(field, h, code, b0 + k, cnt, geo))
+        return out
+    acc['bricks'] += bc[:, 0].tolist()
+    acc['seeds'] += bc[:, 1].tolist()
+    acc['leaks'] += c[:, 3].tolist()
+    voff = torch.cumsum(nv, 0) - nv
+    toff = torch.cumsum(nt, 0) - nt
+    V, T = int(nv.sum()), int(nt.sum())
+    verts = torch.empty(max(V, 1), 3, dtype=torch.float32, device=dev)
+    faces = torch.empty(max(T, 1), 3, dtype=torch.int32, device=dev)
+    offs = torch.stack([voff, toff]).to(dev)
+    _lib.call('ofx_fieldmesh_emit', B, size, level, step, bbmin, scale, _lib.ptr(cws), n, _lib.ptr(ws),
+              _lib.ptr(offs[0]), _lib.ptr(offs[1]), _lib.ptr(verts), _lib.ptr(faces), st)
+    if acc['components'] is not None:
+        return _clean(verts, faces, nv.tolist(), nt.tolist(), acc['components'])
     return [(verts[int(voff[b]):int(voff[b] + nv[b])], faces[int(toff[b]):int(toff[b] + nt[b])]) for b in range(B)]
 
 

@@ -134,7 +134,8 @@ class CascadeSampler:
 
     def _sample_once(self, batch_size, ddim_steps=200, label=None, split_small=None, noises=None, sdf_resolution=None,
                      sdf_scale=0.9, use_graph=None, seed=None, save_index=0, shape_indices=None, timings=None,
-                     mesh=False, mesh_level=0.0, mesh_scale=1.0, mesh_clean=False, octree_mesh=False):
+                     mesh=False, mesh_level=0.0, mesh_scale=1.0, mesh_clean=False, octree_mesh=False,
+                     field_mesh=False, mesh_margin=1):
         """Returns a dict with the per-stage results.  `noises` (optional) = dict of explicit
         init / step noise tensors per stage for reproducible runs.  sdf_resolution (e.g. 256) adds
         out['sdfs'] [B, R, R, R] (needs the VAE).
@@ -151,10 +152,16 @@ class CascadeSampler:
         mesh_clean: keep only each mesh's largest component (the reference's sample(clean=), export_mesh
         clean=True, octfusion_model_union.py:459-467) and add out['mesh_components'], the component counts before
         cleaning; one more host sync (the kept counts).
+        field_mesh (needs sdf_resolution and mesh): mesh the decoded field in octree-guided bricks
+        (mesh.field_mesh, sdf_resolution up to 2048, mesh_margin finest octree cells around the finest nodes) instead
+        of sweeping the lattice: out['meshes'] and out['mesh_stats'] (seeds, bricks, leaks, total_bricks per shape), NO
+        out['sdfs']; two host syncs.
         octree_mesh: also out['octree_meshes'] = per-shape (verts, faces) of the cubes of every node at the small depth
         (voxmesh.octree_mesh; the reference's export_octree, :376,403-422) and, for a 3-stage model,
         out['octree_meshes_large'] at the large depth (octfusion_model_union_3t.py:191); one host sync each."""
         import time as _time
+        if field_mesh and not (sdf_resolution and mesh and self.vae is not None):
+            raise ValueError('field_mesh needs the VAE, sdf_resolution and mesh')
         noises = dict(noises or {})
         out = {}
         S = 1 << self.full_depth
@@ -241,7 +248,17 @@ class CascadeSampler:
         if self.vae is not None:
             out['decoded'] = self.vae.decode_code(x, doctree)
             t0 = lap('vae_decode', t0)
-            if sdf_resolution:
+            if field_mesh:
+                from . import mesh as _mesh
+                cc = {}
+                out['meshes'] = _mesh.field_mesh(out['decoded']['neural_mpu'], sdf_resolution, level=mesh_level,
+                                                 bbmin=-sdf_scale, bbmax=sdf_scale, scale=mesh_scale,
+                                                 margin=mesh_margin, clean=mesh_clean, stats=cc)
+                if mesh_clean:
+                    out['mesh_components'] = cc.pop('components')
+                out['mesh_stats'] = cc
+                t0 = lap('mesh', t0)
+            elif sdf_resolution:
                 out['sdfs'] = mpu.calc_sdf(out['decoded']['neural_mpu'], batch_size, size=sdf_resolution,
                                            bbmin=-sdf_scale, bbmax=sdf_scale)
                 t0 = lap('sdf', t0)

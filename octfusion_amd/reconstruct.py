@@ -137,7 +137,7 @@ def _lap(timings, name, t0, device):
 @torch.no_grad()
 def reconstruct(vae, cfg, inputs, device, sdf_resolution=256, sdf_scale=0.9, level=0.0, clean=False, batch=8, seed=0,
                 points=POINTS, chamfer_points=POINTS, fit=None, mpu_depth=None, out_dir=None, timings=None,
-                metrics=False, thresholds=recon_metrics.THRESHOLDS, occupancy=False):
+                metrics=False, thresholds=recon_metrics.THRESHOLDS, occupancy=False, field_mesh=False, mesh_margin=1):
     """Reconstruct every shape of ``inputs`` (read_inputs) through ``vae``, ``batch`` shapes per call.  cfg:
     recon_config(name), or a dict with depth, full_depth, point_scale.  points: samples per mesh input; fit: factor
     on the normalised mesh samples (default sdf_scale); mpu_depth: depth the SDF is read at (default depth_out);
@@ -151,7 +151,10 @@ def reconstruct(vae, cfg, inputs, device, sdf_resolution=256, sdf_scale=0.9, lev
     that count by the Chamfer score's stride rule; ``null`` for an empty reconstruction.  occupancy: a point-cloud
     input whose directory holds ``points.npz`` gains ``iou``, ``iou_intersection``, ``iou_union`` =
     recon_metrics.occupancy_iou of the batch's ``neural_mpu`` field against that file; any other input gets ``null``
-    and a warning; ``result['fields'][name]`` = (field, batch index)."""
+    and a warning; ``result['fields'][name]`` = (field, batch index).
+    field_mesh: mesh the field in octree-guided bricks (mesh.field_mesh: sdf_resolution up to 2048, a band of
+    mesh_margin finest octree cells around the finest nodes, no dense lattice); each shape's record gains ``mesh_stats``
+    (seeds, bricks, leaks, total_bricks)."""
     device = torch.device(device)
     ps = float(cfg['point_scale'])
     fit = float(sdf_scale if fit is None else fit)
@@ -188,15 +191,23 @@ def reconstruct(vae, cfg, inputs, device, sdf_resolution=256, sdf_scale=0.9, lev
         t0 = _lap(timings, 'octree', t0, device)
         out = vae.forward(octree_in, evaluate=True, mpu_depth=d_mpu)
         t0 = _lap(timings, 'vae_forward', t0, device)
-        sdfs = mpu.calc_sdf(out['neural_mpu'], len(group), size=sdf_resolution, bbmin=-sdf_scale, bbmax=sdf_scale)
-        t0 = _lap(timings, 'sdf', t0, device)
-        recon = mesh.marching_cubes(sdfs, level=level, bbmin=-sdf_scale, bbmax=sdf_scale, scale=ps, clean=clean)
+        fstats = {}
+        if field_mesh:
+            recon = mesh.field_mesh(out['neural_mpu'], sdf_resolution, level=level, bbmin=-sdf_scale, bbmax=sdf_scale,
+                                    scale=ps, margin=mesh_margin, clean=clean, stats=fstats)
+            fstats.pop('components', None)
+        else:
+            sdfs = mpu.calc_sdf(out['neural_mpu'], len(group), size=sdf_resolution, bbmin=-sdf_scale, bbmax=sdf_scale)
+            t0 = _lap(timings, 'sdf', t0, device)
+            recon = mesh.marching_cubes(sdfs, level=level, bbmin=-sdf_scale, bbmax=sdf_scale, scale=ps, clean=clean)
         t0 = _lap(timings, 'mesh', t0, device)
         # ---- score and files
         for k, it in enumerate(group):
             name, (v, f) = it['name'], recon[k]
             rec = {'gt': it['kind'], 'input_points': int(clouds[k].points.shape[0]), 'vertices': int(v.shape[0]),
                    'faces': int(f.shape[0]), 'chamfer_a': None, 'chamfer_b': None, 'obj': None}
+            if field_mesh:
+                rec['mesh_stats'] = {key: int(val[k]) for key, val in fstats.items()}
             if f.shape[0] == 0:
                 warnings.warn('reconstruct: %s: marching cubes found no surface, no mesh written' % name)
             elif chamfer_points:
@@ -247,6 +258,8 @@ def reconstruct(vae, cfg, inputs, device, sdf_resolution=256, sdf_scale=0.9, lev
     res = {'config': cfg.get('name'), 'point_scale': ps, 'sdf_resolution': sdf_resolution, 'sdf_scale': sdf_scale,
            'mpu_depth': d_mpu, 'fit': fit, 'seed': seed, 'chamfer_points': chamfer_points,
            'chamfer_scale': CHAMFER_SCALE, 'shapes': shapes}
+    if field_mesh:
+        res.update(field_mesh=True, mesh_margin=mesh_margin)
     if timings is not None:
         res['phase_seconds'] = dict(timings)
     if out_dir is not None:
@@ -279,6 +292,12 @@ def parser():
                          'only reads ready-made clouds')
     ap.add_argument('--sdf-resolution', type=int, default=256)
     ap.add_argument('--clean', action='store_true', help='keep only the largest connected component of every mesh')
+    ap.add_argument('--field-mesh', action='store_true',
+                    help='mesh the field in octree-guided 8^3-cell bricks instead of sweeping the lattice '
+                         '(mesh.field_mesh): --sdf-resolution may go up to 2048 and every shape of metrics.json gains '
+                         'mesh_stats.  Surface sheets inside coarse leaves, outside the band, are not meshed')
+    ap.add_argument('--mesh-margin', type=int, default=1, metavar='M',
+                    help='with --field-mesh: width of the band around the finest octree nodes, in finest-level cells')
     ap.add_argument('--batch', type=int, default=8, help='shapes per call')
     ap.add_argument('--seed', type=int, default=0, help='seeds the surface sampler and the posterior noise')
     ap.add_argument('--mpu-depth', type=int, default=None,
@@ -308,6 +327,8 @@ def parse_args(argv=None):
         raise ValueError('--points, --batch >= 1, --chamfer-points >= 0 and --sdf-resolution >= 2 are required')
     if any(not t > 0 for t in args.thresholds):
         raise ValueError('--thresholds must be positive')
+    if args.field_mesh and (args.sdf_resolution > mesh.FIELD_MAX_SIZE or args.mesh_margin < 0):
+        raise ValueError('--field-mesh needs --sdf-resolution <= %d and --mesh-margin >= 0' % mesh.FIELD_MAX_SIZE)
     return args
 
 
@@ -335,7 +356,7 @@ def main(argv=None):
                       clean=args.clean, batch=args.batch, seed=args.seed, points=args.points,
                       chamfer_points=args.chamfer_points, fit=args.fit, mpu_depth=args.mpu_depth, out_dir=args.out,
                       timings=timings, metrics=args.metrics, thresholds=tuple(args.thresholds),
-                      occupancy=args.occupancy)
+                      occupancy=args.occupancy, field_mesh=args.field_mesh, mesh_margin=args.mesh_margin)
     res.pop('meshes')
     res.pop('fields', None)
     print(json.dumps(res))
