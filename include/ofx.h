@@ -996,6 +996,64 @@ int ofx_nn_search(const float* q, const int64_t* q_off, const float* t, const in
                   int64_t total_q, int64_t max_q, int64_t max_t, int splits, void* ws, float* dist2, int32_t* idx,
                   void* stream);
 
+/* ------------------------------------------------------------------ normals of raw point clouds (csrc/ofx_normals.hip)
+ * Three stages over `batch` ragged clouds, concatenated: p [N, 3] fp32; off [batch + 1] (int64 device) = where each
+ * cloud begins, off[0] = 0 and the last entry N.  Host-known sizes for the launch geometry: total = N, max_n = the
+ * largest cloud (a cloud larger than stated is not processed in full).  tests/normals_oracle.py restates all three.
+ * Common edges: batch == 0 or total == 0 launches nothing and returns OFX_OK; a negative size, k outside [1, 64],
+ * batch > 65535, total > INT32_MAX, max_n outside [1, total] or a NULL array that would be read or written:
+ * OFX_EINVAL, nothing launched.  Non-finite coordinates are the caller's error (no access leaves the arrays).
+ * ofx_knn: exact k nearest neighbours of every point inside its own cloud.  idx [N, k] int32, local to the cloud,
+ *   d2 [N, k] fp32.
+ *   distance  fma(dz, dz, fma(dy, dy, dx * dx)) from direct fp32 differences, the expression of ofx_nn_search: a
+ *     point against itself gives exactly 0.
+ *   order     a row is ascending by (d2, idx).  The point itself is a candidate; ties go to the lowest index, so an
+ *     exact duplicate with a lower index precedes the point itself.
+ *   small     a cloud with fewer than k points fills the remaining slots with idx = -1, d2 = +inf.
+ *   purity    (idx, d2) is a pure function of the inputs: bitwise equal across repeats, alone or in a batch, and for
+ *     every `cells`.
+ *   cells     each cloud is binned in a uniform grid of c^3 cells over its bounding cube (centred on the box centre,
+ *     side = the largest extent); a query searches shells of cells around its own until its k-th distance lies below
+ *     the squared distance to the unsearched cells, which keeps the result exact.  0 = automatic, per cloud of n
+ *     points c = ofx_knn_cells(n) = clamp(floor(sqrt(n / 32)), 1, 64); c >= 1 forces c^3 cells for every cloud
+ *     (c <= 128 and batch * c^3 < 2^30, else OFX_EINVAL); c = 1 is the brute-force sweep.  A cloud without extent
+ *     uses one cell.
+ *   ws        ofx_knn_ws_bytes(batch, total, max_n, cells) bytes (0 for arguments out of range).
+ * ofx_pca_normals: from the valid (0 <= idx < n) neighbours of each row of idx [N, k], m of them: centroid and
+ *   covariance (divided by m) in fp64 from the fp32 coordinates, summed in neighbour order; eigenvalues l0 <= l1 <= l2
+ *   by a cyclic Jacobi of 8 sweeps in fp64; normals [N, 3] = the eigenvector of l0, normalised in fp64 and rounded
+ *   once to fp32, then negated if its component of largest magnitude (lowest axis on ties, on the fp32 values) is
+ *   negative; variation [N] = fl32(max(l0, 0) / (l0 + l1 + l2)).  m < 3, or an eigenvalue sum that is not positive:
+ *   normal (0, 0, 0), variation 0, and degenerate [batch] int32 (zeroed by the call) counts the point.
+ * ofx_orient_normals: a consistent outward sign, every cloud on its own.  n [N, 3] unoriented normals, idx [N, k]
+ *   as ofx_knn writes it; per cloud lo [batch, 3], e [batch] fp32 (the corner and the side of the bounding cube,
+ *   e > 0) and g [batch] int32 (cells per axis, 8 <= g <= max_g <= 128; max_g is host-known and sizes ws =
+ *   ofx_orient_normals_ws_bytes(batch, total, max_g)); 1 <= steps <= 64, 0 <= rounds <= 64.
+ *   grid      h = fl32(e / g); (g + 2)^3 cells with one border layer; c(x) = floor(fl32(fl32(x - lo) / h)) per axis.
+ *     The cell of a point is clamp(c, 0, g - 1) + 1.  occupied = cells holding a point, dilated by the
+ *     6-neighbourhood (the border layer included); exterior = the 6-connected set of non-occupied cells reachable from
+ *     the non-occupied cells of the border layer.
+ *   march     for s = 1 .. 2 steps: q = fl32(p + fl32(fl32(s * fl32(h / 2)) * n)); a = the first s at which c(q) + 1
+ *     is outside [0, g + 1] on some axis (or not a number) or names an exterior cell, 2 steps + 1 if none; b likewise
+ *     along -n.  sign = +1 if a < b, -1 if b < a, else 0 (undecided).
+ *   votes     `rounds` double-buffered rounds: d_i = sum over the valid neighbours j of row i, in neighbour order, of
+ *     s_j * ((n_j.x * n_i.x + n_j.y * n_i.y) + n_j.z * n_i.z) in fp64 from the fp32 components; s_i <- sign(d_i),
+ *     unchanged when d_i = 0.
+ *   outputs   out [N, 3] = -n where the final sign is -1, else n (an undecided point keeps the PCA sign); sign [N]
+ *     int8 = the final sign (may be NULL); counts [batch, 4] int32 (zeroed by the call) = undecided_after_march,
+ *     flipped_by_vote (marched sign non-zero and the final sign its opposite), undecided (final sign 0),
+ *     degenerate (n = (0, 0, 0)).  All of it is a pure function of the inputs: the flood's result is a set. */
+int ofx_knn_cells(int64_t n);
+size_t ofx_knn_ws_bytes(int batch, int64_t total, int64_t max_n, int cells);
+int ofx_knn(const float* p, const int64_t* off, int batch, int64_t total, int64_t max_n, int k, int cells, void* ws,
+            int32_t* idx, float* d2, void* stream);
+int ofx_pca_normals(const float* p, const int64_t* off, const int32_t* idx, int batch, int64_t total, int64_t max_n,
+                    int k, float* normals, float* variation, int32_t* degenerate, void* stream);
+size_t ofx_orient_normals_ws_bytes(int batch, int64_t total, int max_g);
+int ofx_orient_normals(const float* p, const float* n, const int64_t* off, const int32_t* idx, int batch, int64_t total,
+                       int64_t max_n, int k, const float* lo, const float* e, const int32_t* g, int max_g, int steps,
+                       int rounds, void* ws, float* out, int8_t* sign, int32_t* counts, void* stream);
+
 /* ------------------------------------------------------------------ SDF training samples (csrc/ofx_sdfdata.hip)
  * The reference's tools/repair_mesh.py sample_sdf (:293-334) and sample_occu (:358-375) on an SDF lattice
  * sdf [S, S, S] fp32, x slowest (the reference's sdf[x, y, z]); tests/sdfdata_oracle.py restates both with numpy.

@@ -205,6 +205,13 @@ _SIGS = {
     'ofx_nn_search_splits': (c_i, [c_i, c_l, c_l], False),
     'ofx_nn_search_ws_bytes': (c_sz, [c_l], False),
     'ofx_nn_search': (c_i, [c_p, c_p, c_p, c_p, c_i, c_l, c_l, c_l, c_i, c_p, c_p, c_p, c_p], True),
+    'ofx_knn_cells': (c_i, [c_l], False),
+    'ofx_knn_ws_bytes': (c_sz, [c_i, c_l, c_l, c_i], False),
+    'ofx_knn': (c_i, [c_p, c_p, c_i, c_l, c_l, c_i, c_i, c_p, c_p, c_p, c_p], True),
+    'ofx_pca_normals': (c_i, [c_p, c_p, c_p, c_i, c_l, c_l, c_i, c_p, c_p, c_p, c_p], True),
+    'ofx_orient_normals_ws_bytes': (c_sz, [c_i, c_l, c_i], False),
+    'ofx_orient_normals': (c_i, [c_p, c_p, c_p, c_p, c_i, c_l, c_l, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p,
+                                 c_p, c_p], True),
     'ofx_sdf_sample_ws_bytes': (c_sz, [c_l, c_i], False),
     'ofx_sdf_sample_nodes': (c_i, [c_p, c_i, c_p, c_l, c_p, c_i, c_i, c_i, c_u64, c_l, c_p, c_f, c_p, c_p, c_p, c_p, c_p,
                                    c_p], True),

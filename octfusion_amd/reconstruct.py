@@ -20,6 +20,10 @@ octree_in, evaluate=True) -> get_sdfs -> export_mesh -> input.ply) and of ``calc
   completeness, accuracy, normal consistency, F-score at ``--thresholds``) and ``--occupancy`` the volumetric IoU
   against the ``points.npz`` beside a point-cloud input: octfusion_amd.recon_metrics, DESIGN.md 4.15.  Without them
   metrics.json is what it was.
+* ``--estimate-normals`` takes clouds that carry no normals -- a ``pointcloud.npz`` without the ``normals`` key, a bare
+  ``.npy`` / ``.npz`` (key ``points``) or a ``.ply`` -- and estimates them on the device before the ``Points`` are
+  built (octfusion_amd.normals); such a shape's record gains ``normals`` (k, the grid size and the
+  orientation counts).  An input that has normals takes exactly the path it takes without the flag.
 
     python -m octfusion_amd.reconstruct --config snet_uncond --vae vae.pth --input data/02691156/1a04e3 --out recon
     python -m octfusion_amd.reconstruct --config snet_uncond --vae vae.pth --from-mesh --input samples/0.obj --out recon
@@ -33,7 +37,7 @@ import warnings
 import numpy as np
 import torch
 
-from . import configs, mesh, metrics, mpu, recon_metrics
+from . import configs, mesh, metrics, mpu, normals, recon_metrics
 from .metrics import sample_surface          # reconstruct() has an argument called metrics
 from .octree import Points, build_octree_batch
 
@@ -64,9 +68,31 @@ def shape_name(path):
     return name
 
 
-def read_inputs(paths, from_mesh=False):
+def _read_raw(path):
+    """(points, normals or None) of an input of --estimate-normals: a directory with pointcloud.npz, that file, or a
+    bare .npy / .npz / .ply cloud."""
+    low = path.lower()
+    if os.path.isdir(path) or os.path.basename(path) == 'pointcloud.npz':
+        low = path = path if os.path.basename(path) == 'pointcloud.npz' else os.path.join(path, 'pointcloud.npz')
+    nrm = None
+    if low.endswith('.npz'):
+        with np.load(path) as z:
+            pts = np.asarray(z['points'], np.float32)
+            if 'normals' in z.files:
+                nrm = np.asarray(z['normals'], np.float32)
+    elif low.endswith('.ply'):
+        pts, nrm = mesh.read_ply(path)
+    else:
+        pts = normals.read_cloud(path)
+    if pts.ndim != 2 or pts.shape[1] != 3 or (nrm is not None and nrm.shape != pts.shape):
+        raise ValueError('reconstruct: %s: points %s, normals %s' % (path, pts.shape, None if nrm is None else nrm.shape))
+    return pts, nrm
+
+
+def read_inputs(paths, from_mesh=False, estimate_normals=False):
     """[{name, kind, path, points + normals | verts + faces}] (numpy, file units) of the input paths; kind 'points' for
-    a directory with pointcloud.npz (or the file itself), 'mesh' for an OBJ with from_mesh."""
+    a directory with pointcloud.npz (or the file itself), 'mesh' for an OBJ with from_mesh.  estimate_normals: a point
+    input may also be a bare .npy / .npz / .ply file, and may lack normals (``normals`` is then None)."""
     out, seen = [], set()
     for p in paths:
         name = shape_name(p)
@@ -80,6 +106,9 @@ def read_inputs(paths, from_mesh=False):
             if len(f) == 0:
                 raise ValueError('reconstruct: %s has no faces' % p)
             out.append({'name': name, 'kind': 'mesh', 'path': p, 'verts': v, 'faces': f})
+        elif estimate_normals:
+            pts, nrm = _read_raw(p)
+            out.append({'name': name, 'kind': 'points', 'path': p, 'points': pts, 'normals': nrm})
         else:
             f = p if os.path.basename(p) == 'pointcloud.npz' else os.path.join(p, 'pointcloud.npz')
             with np.load(f) as z:
@@ -137,7 +166,8 @@ def _lap(timings, name, t0, device):
 @torch.no_grad()
 def reconstruct(vae, cfg, inputs, device, sdf_resolution=256, sdf_scale=0.9, level=0.0, clean=False, batch=8, seed=0,
                 points=POINTS, chamfer_points=POINTS, fit=None, mpu_depth=None, out_dir=None, timings=None,
-                metrics=False, thresholds=recon_metrics.THRESHOLDS, occupancy=False, field_mesh=False, mesh_margin=1):
+                metrics=False, thresholds=recon_metrics.THRESHOLDS, occupancy=False, field_mesh=False, mesh_margin=1,
+                estimate_normals=False, normal_k=16):
     """Reconstruct every shape of ``inputs`` (read_inputs) through ``vae``, ``batch`` shapes per call.  cfg:
     recon_config(name), or a dict with depth, full_depth, point_scale.  points: samples per mesh input; fit: factor
     on the normalised mesh samples (default sdf_scale); mpu_depth: depth the SDF is read at (default depth_out);
@@ -154,7 +184,10 @@ def reconstruct(vae, cfg, inputs, device, sdf_resolution=256, sdf_scale=0.9, lev
     and a warning; ``result['fields'][name]`` = (field, batch index).
     field_mesh: mesh the field in octree-guided bricks (mesh.field_mesh: sdf_resolution up to 2048, a band of
     mesh_margin finest octree cells around the finest nodes, no dense lattice); each shape's record gains ``mesh_stats``
-    (seeds, bricks, leaks, total_bricks)."""
+    (seeds, bricks, leaks, total_bricks).
+    estimate_normals: a point input whose ``normals`` is None gets them from normals.estimate_normals(k=normal_k) on the
+    device, all such clouds of a group in one call; its record gains ``normals`` = {k, G, undecided_after_march,
+    flipped_by_vote, undecided, degenerate}.  Without it such an input is an error."""
     device = torch.device(device)
     ps = float(cfg['point_scale'])
     fit = float(sdf_scale if fit is None else fit)
@@ -177,10 +210,20 @@ def reconstruct(vae, cfg, inputs, device, sdf_resolution=256, sdf_scale=0.9, lev
                 clouds[k] = Points(p[j] * fit, n[j])
                 c, s = _frame(vf[j][0])
                 gts[k] = ((vf[j][0] - c) * (s * fit * ps), vf[j][1])        # the input mesh in the output frame
+        raw_pos = [k for k, it in enumerate(group) if it['kind'] == 'points' and it['normals'] is None]
+        if raw_pos and not estimate_normals:
+            raise ValueError('reconstruct: %s has no normals (estimate_normals is off)' % group[raw_pos[0]]['path'])
+        est, nstats = {}, {}
+        if raw_pos:
+            got = normals.estimate_normals([torch.from_numpy(group[k]['points']).to(device) / ps for k in raw_pos],
+                                           k=normal_k, stats=nstats)
+            est = dict(zip(raw_pos, got))
+            nstats = {k: dict({'k': int(normal_k), 'G': nstats['G'][j]}, **{c: nstats[c][j] for c in normals.COUNTS})
+                      for j, k in enumerate(raw_pos)}
         for k, it in enumerate(group):
             if it['kind'] == 'points':
                 clouds[k] = Points(torch.from_numpy(it['points']).to(device) / ps,
-                                   torch.from_numpy(it['normals']).to(device))
+                                   est[k] if k in est else torch.from_numpy(it['normals']).to(device))
         for k, c in enumerate(clouds):
             c.clip(-1.0, 1.0)
             if c.points.shape[0] == 0:
@@ -208,6 +251,8 @@ def reconstruct(vae, cfg, inputs, device, sdf_resolution=256, sdf_scale=0.9, lev
                    'faces': int(f.shape[0]), 'chamfer_a': None, 'chamfer_b': None, 'obj': None}
             if field_mesh:
                 rec['mesh_stats'] = {key: int(val[k]) for key, val in fstats.items()}
+            if k in nstats:
+                rec['normals'] = nstats[k]
             if f.shape[0] == 0:
                 warnings.warn('reconstruct: %s: marching cubes found no surface, no mesh written' % name)
             elif chamfer_points:
@@ -315,6 +360,11 @@ def parser():
                          '--chamfer-points samples per side (%d when that is 0)' % POINTS)
     ap.add_argument('--thresholds', type=float, nargs='+', default=list(recon_metrics.THRESHOLDS), metavar='T',
                     help='with --metrics: the F-score distance thresholds, in file units')
+    ap.add_argument('--estimate-normals', action='store_true',
+                    help='accept clouds without normals (pointcloud.npz without the key, bare .npy / .npz / .ply) and '
+                         'estimate oriented normals on the device (octfusion_amd.normals)')
+    ap.add_argument('--normal-k', type=int, default=16, metavar='K',
+                    help='with --estimate-normals: neighbours per point (1..%d)' % normals.MAX_K)
     ap.add_argument('--occupancy', action='store_true',
                     help='add the volumetric IoU against the points.npz beside a pointcloud.npz input '
                          '(recon_metrics.occupancy_iou)')
@@ -329,6 +379,10 @@ def parse_args(argv=None):
         raise ValueError('--thresholds must be positive')
     if args.field_mesh and (args.sdf_resolution > mesh.FIELD_MAX_SIZE or args.mesh_margin < 0):
         raise ValueError('--field-mesh needs --sdf-resolution <= %d and --mesh-margin >= 0' % mesh.FIELD_MAX_SIZE)
+    if not 1 <= args.normal_k <= normals.MAX_K:
+        raise ValueError('--normal-k must be in [1, %d]' % normals.MAX_K)
+    if args.estimate_normals and args.from_mesh:
+        raise ValueError('--estimate-normals is for point inputs; --from-mesh samples face normals')
     return args
 
 
@@ -346,7 +400,7 @@ def build_vae(config, vae_ckpt=None, allow_pickle=False):
 
 def main(argv=None):
     args = parse_args(argv)
-    inputs = read_inputs(args.input, args.from_mesh)
+    inputs = read_inputs(args.input, args.from_mesh, args.estimate_normals)
     from . import _lib
     _lib.require_device()
     device = torch.device('cuda', torch.cuda.current_device())
@@ -356,7 +410,8 @@ def main(argv=None):
                       clean=args.clean, batch=args.batch, seed=args.seed, points=args.points,
                       chamfer_points=args.chamfer_points, fit=args.fit, mpu_depth=args.mpu_depth, out_dir=args.out,
                       timings=timings, metrics=args.metrics, thresholds=tuple(args.thresholds),
-                      occupancy=args.occupancy, field_mesh=args.field_mesh, mesh_margin=args.mesh_margin)
+                      occupancy=args.occupancy, field_mesh=args.field_mesh, mesh_margin=args.mesh_margin,
+                      estimate_normals=args.estimate_normals, normal_k=args.normal_k)
     res.pop('meshes')
     res.pop('fields', None)
     print(json.dumps(res))
