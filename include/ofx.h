@@ -1112,6 +1112,44 @@ int ofx_mesh_sdf(const float* verts, const int32_t* faces, const int64_t* vert_o
  * bins), words[2] += triangles evaluated after the per-triangle box test (x 64 = point-triangle pairs).  Sticky. */
 int ofx_mesh_sdf_set_counters(unsigned long long* words);
 
+/* ------------------------------------------------------------------ point -> mesh queries (csrc/ofx_meshquery.hip)
+ * Exact distance, nearest face and closest point of arbitrary points against triangle meshes: the search of
+ * ofx_mesh_sdf off the lattice.  tests/meshquery_oracle.py restates the contract in float64.  Meshes concatenated as
+ * for ofx_mesh_sdf (verts, faces, vert_off, tri_off); queries as for ofx_nn_search: q [Q, 3] fp32, q_off [batch + 1]
+ * (int64 device) = where each shape's queries begin, the last entry Q = total_q.  A shape may have zero queries.
+ * max_q = the largest query count of one shape (host-known; the grid is ceil(max_q / 64) x batch waves).
+ *   dist [Q] fp32  the Euclidean distance from the query to the nearest point of the nearest triangle of its shape: the
+ *     minimum over ALL the shape's triangles of the fixed fp64 expression of (point, triangle) that ofx_mesh_sdf
+ *     minimises (the same code), rounded once.  At a query that is a lattice point the value is ofx_mesh_sdf's, bit
+ *     for bit.  signed_ != 0: negated where the number of crossings with x_cross <= (double)q.x is odd -- the crossing
+ *     rule, the x_cross expression and the edge tie rule of ofx_mesh_sdf (the same code); an open mesh gives the parity.
+ *   face [Q] int32  the 0-based index, within the shape's own faces, of a triangle that attains the minimum: among the
+ *     triangles whose computed squared distance is equal as doubles, the lowest index.
+ *   point [Q, 3] fp32 (may be NULL)  the closest point on that triangle, evaluated once from the face's original
+ *     vertices in fp64 with the pair's branches (the three edges as clamped segments, a later edge only if strictly
+ *     nearer; the plane where the projection falls inside and is strictly nearer), rounded once.
+ *   A query with a non-finite coordinate gets dist = NaN, face = -1, point = NaN; it does not enter its wave's box and
+ *   changes no other query's result.
+ *   status [batch] int32: non-zero, and that shape's outputs left unwritten, under the conditions of ofx_mesh_sdf (a
+ *     face index outside [0, V_b), a non-finite vertex used by a face); nothing is read through such an index.  A
+ *     shape needs >= 1 face (the caller checks).  The status words are written even when total_q == 0.
+ *   bins: the grid size G per shape, 1 .. 16, or 0 = automatic: per shape the smallest G in 1 .. 16 with
+ *     256 G^2 >= F_b (a surface meets about 3 G^2 bins: at most about 85 triangles per occupied bin).  The grid spans
+ *     each shape's own bounding box (of the vertices its valid faces use), so a mesh may live in any frame.
+ *   The output is a pure function of the inputs, bitwise: the same alone or in a batch, for any order of the queries
+ *   and for any bins (bins and order only decide what is skipped, and every skip compares a lower bound with an upper
+ *   bound, with a margin).  ws: ofx_mesh_query_ws_bytes (0 for arguments out of range: batch in [1, 65535],
+ *   total_verts >= 1, 1 <= total_faces < 2^31, 0 <= total_q <= 2^30, bins in [0, 16]); it holds the binned triangles
+ *   with their face index (40 bytes per face).  Bad arguments: OFX_EINVAL, nothing launched. */
+size_t ofx_mesh_query_ws_bytes(int batch, int64_t total_verts, int64_t total_faces, int64_t total_q, int bins);
+int ofx_mesh_query(const float* verts, const int32_t* faces, const int64_t* vert_off, const int64_t* tri_off,
+                   const float* q, const int64_t* q_off, int batch, int64_t total_q, int64_t max_q, int bins,
+                   int signed_, float* dist, int32_t* face, float* point, void* ws, int32_t* status, void* stream);
+/* Measurement aid (tools/meshquery_probe.py; not on the operator path), as ofx_mesh_sdf_set_counters: per wave of 64
+ * queries the distance pass adds words[0] += bins searched, words[1] += triangles staged, words[2] += triangles
+ * evaluated after the per-triangle box test (x 64 = point-triangle pairs).  NULL: counting off.  Sticky. */
+int ofx_mesh_query_set_counters(unsigned long long* words);
+
 /* ------------------------------------------------------------------ rendering (csrc/ofx_render.hip)
  * Shaded views of triangle meshes for the reference's FID image sets (utils/render_utils.py:14-23, utils/render/):
  * a deterministic renderer of the project's own, parity with pyrender unpinned; tests/render_oracle.py

@@ -28,18 +28,16 @@
 
 #pragma clang fp contract(off)
 
+#include "ofx_tri.h"          // the bounds, the pair and the crossing: shared with ofx_meshquery.hip
+
 namespace {
 
-constexpr int MS_T = 64;           // one wave per block: a brick of 4^3 points / a tile of 8 x 8 columns
-constexpr int MS_BRICK = 4;
+constexpr int MS_BRICK = 4;        // one wave (MS_T lanes) per block: a brick of 4^3 points / a tile of 8 x 8 columns
 constexpr int MS_TILE = 8;
 constexpr int MS_BIN_CELLS = 8;    // lattice cells per bin edge (until the cap below)
 constexpr int MS_MAX_G = 16;       // at most 16^3 bins per shape
 constexpr int MS_MAX_SIZE = 512;
 constexpr int MS_PREP_T = 256;
-constexpr int MS_REC = 16;         // doubles per staged triangle
-constexpr float MS_REL = 1.0e-3f;  // margins of every skip: relative, and absolute in squared distance
-constexpr float MS_ABS = 1.0e-4f;
 
 __host__ __device__ inline int ms_bins(int S) {
   const int g = (S + MS_BIN_CELLS - 1) / MS_BIN_CELLS;
@@ -47,13 +45,6 @@ __host__ __device__ inline int ms_bins(int S) {
 }
 
 __device__ __forceinline__ double ms_lat(int i, int S) { return (2.0 * (double)i) / (double)S - 1.0; }
-
-// order-preserving int key of a float
-__device__ __forceinline__ int32_t ms_key(float f) {
-  const int32_t b = __float_as_int(f);
-  return b >= 0 ? b : b ^ 0x7fffffff;
-}
-__device__ __forceinline__ float ms_unkey(int32_t k) { return __int_as_float(k >= 0 ? k : k ^ 0x7fffffff); }
 
 struct MsWs {
   int32_t* cnt;      // [batch * G3]      triangles per bin
@@ -94,38 +85,6 @@ struct MsMesh {
   int batch, S, G;
 };
 
-// Shape of global triangle t (tri_off is non-decreasing; batch is small).
-__device__ __forceinline__ int ms_shape_of(const MsMesh& m, int64_t t) {
-  int lo = 0, hi = m.batch - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (m.tri_off[mid] <= t) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
-// The nine coordinates of triangle t of shape b; false (nothing read past the shape) if an index is out of range or a
-// coordinate is not finite.
-__device__ __forceinline__ bool ms_load(const MsMesh& m, int64_t t, int b, float (&c)[9]) {
-  const int64_t v0 = m.vert_off[b], nv = m.vert_off[b + 1] - v0;
-  bool ok = true;
-  int32_t id[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    id[k] = m.faces[t * 3 + k];
-    ok = ok && id[k] >= 0 && (int64_t)id[k] < nv;
-  }
-  if (!ok) return false;
-#pragma unroll
-  for (int k = 0; k < 3; ++k)
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      c[k * 3 + a] = m.verts[(v0 + id[k]) * 3 + a];
-      ok = ok && isfinite(c[k * 3 + a]);
-    }
-  return ok;
-}
-
 __device__ __forceinline__ int ms_bin_of(const MsMesh& m, const float (&c)[9]) {
   int g[3];
 #pragma unroll
@@ -162,9 +121,9 @@ __global__ __launch_bounds__(MS_PREP_T) void ms_bin_kernel(MsMesh m, MsWs w, int
   const int64_t stride = (int64_t)gridDim.x * MS_PREP_T;
   const int G3 = m.G * m.G * m.G;
   for (int64_t t = (int64_t)blockIdx.x * MS_PREP_T + threadIdx.x; t < total; t += stride) {
-    const int b = ms_shape_of(m, t);
+    const int b = ms_shape_of(m.tri_off, m.batch, t);
     float c[9];
-    if (!ms_load(m, t, b, c)) {
+    if (!ms_load(m.verts, m.faces, m.vert_off, t, b, c)) {
       if (!FILL) atomicOr(&status[b], 1);
       continue;
     }
@@ -181,151 +140,6 @@ __global__ __launch_bounds__(MS_PREP_T) void ms_bin_kernel(MsMesh m, MsWs w, int
 #pragma unroll
       for (int k = 0; k < 9; ++k) w.tri[slot * 9 + k] = c[k];
     }
-  }
-}
-
-__device__ __forceinline__ float ms_wave_max(float v) {
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) v = fmaxf(v, __shfl_xor(v, s));
-  return v;
-}
-
-// squared smallest / largest distance between the boxes [alo, ahi] and [blo, bhi]
-__device__ __forceinline__ float ms_box_min2(const float (&alo)[3], const float (&ahi)[3], const float (&blo)[3],
-                                             const float (&bhi)[3]) {
-  float s = 0.f;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const float g = fmaxf(0.f, fmaxf(blo[a] - ahi[a], alo[a] - bhi[a]));
-    s += g * g;
-  }
-  return s;
-}
-__device__ __forceinline__ float ms_box_max2(const float (&alo)[3], const float (&ahi)[3], const float (&blo)[3],
-                                             const float (&bhi)[3]) {
-  float s = 0.f;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const float g = fmaxf(fabsf(bhi[a] - alo[a]), fabsf(ahi[a] - blo[a]));
-    s += g * g;
-  }
-  return s;
-}
-__device__ __forceinline__ bool ms_beyond(float lower, float upper) { return lower * (1.f - MS_REL) > upper + MS_ABS; }
-
-__device__ __forceinline__ double ms_dot(const double (&u)[3], const double (&v)[3]) {
-  return (u[0] * v[0] + u[1] * v[1]) + u[2] * v[2];
-}
-__device__ __forceinline__ void ms_cross(const double (&u)[3], const double (&v)[3], double (&r)[3]) {
-  r[0] = u[1] * v[2] - u[2] * v[1];
-  r[1] = u[2] * v[0] - u[0] * v[2];
-  r[2] = u[0] * v[1] - u[1] * v[0];
-}
-__device__ __forceinline__ double ms_inv(double x) { return x > 0.0 ? 1.0 / x : 0.0; }
-
-// squared distance from the end of `ap` (= p - a) to the segment a + t e, t in [0, 1]; ie = 1 / |e|^2 or 0
-__device__ __forceinline__ double ms_seg2(const double (&ap)[3], const double (&e)[3], double ie) {
-  double t = ms_dot(ap, e) * ie;
-  t = t < 0.0 ? 0.0 : (t > 1.0 ? 1.0 : t);
-  double d[3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) d[a] = ap[a] - t * e[a];
-  return ms_dot(d, d);
-}
-
-// Search one bin's triangles [start, start + count) for the brick: lane's point p, running best (squared).
-template <bool COUNT>
-__device__ __forceinline__ void ms_search_bin(const float* __restrict__ tri, int64_t start, int count, int lane,
-                                              const float (&klo)[3], const float (&khi)[3], const double (&p)[3],
-                                              double& best, double* rec, uint32_t (&tally)[3]) {
-  if (COUNT) {
-    tally[0] += 1u;
-    tally[1] += (uint32_t)count;
-  }
-  for (int base = 0; base < count; base += MS_T) {
-    const int t = base + lane;
-    bool keep = t < count;
-    const float worst = ms_wave_max((float)best);
-    if (keep) {
-      float c[9];
-#pragma unroll
-      for (int k = 0; k < 9; ++k) c[k] = tri[(start + t) * 9 + k];
-      float lo[3], hi[3];
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        lo[a] = fminf(fminf(c[a], c[3 + a]), c[6 + a]);
-        hi[a] = fmaxf(fmaxf(c[a], c[3 + a]), c[6 + a]);
-      }
-      keep = !ms_beyond(ms_box_min2(klo, khi, lo, hi), worst);
-      if (keep) {
-        double A[3], ab[3], bc[3], ca[3], n[3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-          A[a] = (double)c[a];
-          ab[a] = (double)c[3 + a] - (double)c[a];
-          bc[a] = (double)c[6 + a] - (double)c[3 + a];
-          ca[a] = (double)c[a] - (double)c[6 + a];
-        }
-        ms_cross(ab, bc, n);
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-          rec[a * MS_T + lane] = A[a];
-          rec[(3 + a) * MS_T + lane] = ab[a];
-          rec[(6 + a) * MS_T + lane] = bc[a];
-          rec[(9 + a) * MS_T + lane] = n[a];
-        }
-        rec[12 * MS_T + lane] = ms_inv(ms_dot(ab, ab));
-        rec[13 * MS_T + lane] = ms_inv(ms_dot(bc, bc));
-        rec[14 * MS_T + lane] = ms_inv(ms_dot(ca, ca));
-        rec[15 * MS_T + lane] = ms_inv(ms_dot(n, n));
-      }
-    }
-    __syncthreads();
-    uint64_t mask = __ballot(keep);
-    if (COUNT) tally[2] += (uint32_t)__popcll(mask);
-    while (mask) {
-      const int j = __ffsll((unsigned long long)mask) - 1;
-      mask &= mask - 1;
-      double ab[3], bc[3], ca[3], n[3], ap[3], bp[3], cp[3];
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        ab[a] = rec[(3 + a) * MS_T + j];
-        bc[a] = rec[(6 + a) * MS_T + j];
-        n[a] = rec[(9 + a) * MS_T + j];
-        ca[a] = -(ab[a] + bc[a]);          // only a direction for the clamp and the inside test of edge c -> a
-        ap[a] = p[a] - rec[a * MS_T + j];
-        bp[a] = ap[a] - ab[a];
-        cp[a] = bp[a] - bc[a];
-      }
-      double d = ms_seg2(ap, ab, rec[12 * MS_T + j]);
-      d = fmin(d, ms_seg2(bp, bc, rec[13 * MS_T + j]));
-      d = fmin(d, ms_seg2(cp, ca, rec[14 * MS_T + j]));
-      const double inn = rec[15 * MS_T + j];
-      if (inn > 0.0) {
-        double x[3];
-        ms_cross(ab, ap, x);
-        const double s0 = ms_dot(n, x);
-        ms_cross(bc, bp, x);
-        const double s1 = ms_dot(n, x);
-        ms_cross(ca, cp, x);
-        const double s2 = ms_dot(n, x);
-        if (s0 >= 0.0 && s1 >= 0.0 && s2 >= 0.0) {
-          const double h = ms_dot(n, ap);
-          d = fmin(d, (h * h) * inn);
-        }
-      }
-      best = fmin(best, d);
-    }
-    __syncthreads();
-  }
-}
-
-__device__ __forceinline__ void ms_bin_box(const int32_t* __restrict__ box, int64_t bin, float (&lo)[3],
-                                           float (&hi)[3]) {
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    lo[a] = ms_unkey(box[bin * 6 + a]);
-    hi[a] = ms_unkey(box[bin * 6 + 3 + a]);
   }
 }
 
@@ -387,8 +201,9 @@ __global__ __launch_bounds__(MS_T) void ms_dist_kernel(int S, int G, MsWs w, con
   const float upper = u_best * (1.f + MS_REL) + MS_ABS;
 
   double best = INFINITY;
-  ms_search_bin<COUNT>(w.tri, w.off[bin0 + u_bin], w.off[bin0 + u_bin + 1] - w.off[bin0 + u_bin], lane, klo, khi, p,
-                       best, rec, tally);
+  int32_t none = 0;                              // the lattice keeps no face
+  ms_search_bin<COUNT, false>(w.tri, w.off[bin0 + u_bin], w.off[bin0 + u_bin + 1] - w.off[bin0 + u_bin], lane, klo, khi,
+                              p, best, none, rec, nullptr, tally);
 
   // pass 2: every other bin that can still hold a nearer triangle
   for (int g0 = 0; g0 < G3; g0 += MS_T) {
@@ -407,7 +222,8 @@ __global__ __launch_bounds__(MS_T) void ms_dist_kernel(int S, int G, MsWs w, con
       float lo[3], hi[3];
       ms_bin_box(w.box, bin, lo, hi);
       if (ms_beyond(ms_box_min2(klo, khi, lo, hi), ms_wave_max((float)best))) continue;
-      ms_search_bin<COUNT>(w.tri, w.off[bin], w.off[bin + 1] - w.off[bin], lane, klo, khi, p, best, rec, tally);
+      ms_search_bin<COUNT, false>(w.tri, w.off[bin], w.off[bin + 1] - w.off[bin], lane, klo, khi, p, best, none, rec,
+                                  nullptr, tally);
     }
   }
   if (live) sdf[(((int64_t)b * S + idx[0]) * S + idx[1]) * S + idx[2]] = (float)sqrt(best);
@@ -415,27 +231,6 @@ __global__ __launch_bounds__(MS_T) void ms_dist_kernel(int S, int G, MsWs w, con
 }
 
 // ---- sign ---------------------------------------------------------------------------------------------------------
-// a*b - c*d with one rounding of the result (Kahan); exact whenever the products are
-__device__ __forceinline__ double ms_det2(double a, double b, double c, double d) {
-  const double w = c * d;
-  const double e = fma(-c, d, w);
-  const double f = fma(a, b, -w);
-  return f + e;
-}
-
-// Edge function of the directed edge u -> v at q, (v - u) x (q - u) in the yz-plane, on the canonical ordering of the
-// end points; sgn = its sign at q + (eps, eps^2).  Reversing the edge negates both, bit for bit.
-__device__ __forceinline__ double ms_edge(double uy, double uz, double vy, double vz, double qy, double qz, int& sgn) {
-  const bool flip = vy < uy || (vy == uy && vz < uz);
-  const double ay = flip ? vy : uy, az = flip ? vz : uz, by = flip ? uy : vy, bz = flip ? uz : vz;
-  const double dy = by - ay, dz = bz - az;
-  const double e = ms_det2(dy, qz - az, dz, qy - ay);
-  int s = e > 0.0 ? 1 : (e < 0.0 ? -1 : 0);
-  if (s == 0) s = dz != 0.0 ? (dz > 0.0 ? -1 : 1) : (dy > 0.0 ? 1 : -1);
-  sgn = flip ? -s : s;
-  return flip ? -e : e;
-}
-
 __global__ __launch_bounds__(MS_T) void ms_sign_kernel(int S, int G, MsWs w, const int32_t* __restrict__ status,
                                                        float* __restrict__ sdf) {
   __shared__ double rec[MS_REC * MS_T];
@@ -479,7 +274,7 @@ __global__ __launch_bounds__(MS_T) void ms_sign_kernel(int S, int G, MsWs w, con
           const double y0 = c[1], z0 = c[2], y1 = c[4], z1 = c[5], y2 = c[7], z2 = c[8];
           keep = fmin(fmin(y0, y1), y2) <= yhi && fmax(fmax(y0, y1), y2) >= ylo &&
                  fmin(fmin(z0, z1), z2) <= zhi && fmax(fmax(z0, z1), z2) >= zlo;
-          const double area = ms_det2(y1 - y0, z2 - z0, z1 - z0, y2 - y0);
+          const double area = ms_proj_area(y0, z0, y1, z1, y2, z2);
           keep = keep && area != 0.0;           // a projection of zero area never counts
           if (keep) {
             rec[0 * MS_T + lane] = y0;
@@ -506,7 +301,7 @@ __global__ __launch_bounds__(MS_T) void ms_sign_kernel(int S, int G, MsWs w, con
           ms_edge(y1, z1, y2, z2, py, pz, s1);
           const double e20 = ms_edge(y2, z2, y0, z0, py, pz, s2);     // weight of vertex 1
           if (s0 == s1 && s1 == s2) {
-            const double x = rec[6 * MS_T + q] + (e01 * rec[8 * MS_T + q] + e20 * rec[7 * MS_T + q]) / rec[9 * MS_T + q];
+            const double x = ms_cross_x(rec, q, e01, e20);
             // the first lattice index whose x is not left of the crossing
             double f = ceil((x + 1.0) * 0.5 * (double)S);
             f = f < 0.0 ? 0.0 : (f > (double)S ? (double)S : f);

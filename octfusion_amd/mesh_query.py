@@ -1,0 +1,166 @@
+"""Exact point-to-mesh queries on the device (csrc/ofx_meshquery.hip, ``ofx_mesh_query``): what Kaolin, PyTorch3D,
+libigl and trimesh call point-to-mesh distance / closest point, with the search and the arithmetic of ``mesh_to_sdf``.
+
+* ``closest_point``  per query point the distance to the nearest triangle (optionally signed by ray parity), that
+                     triangle's index and the closest point on it, for a batch of meshes with ragged query sets in one
+                     call.  Meshes may live in any frame.
+* ``mesh_error``     how far two meshes are apart: surface samples of each measured exactly against the other's
+                     triangles (mean, rms, max per direction, and the Hausdorff distance of the samples).
+
+    python -m octfusion_amd.mesh_query --a A.obj --b B.obj [--samples N] [--signed]
+
+tests/meshquery_oracle.py restates the contract in numpy float64.  There is no CPU path.
+"""
+import argparse
+import json
+
+import numpy as np
+import torch
+
+from . import _lib, mesh, metrics
+from ._lib import call, ptr, stream
+
+MAX_BINS = 16
+_INT32_MAX = 2 ** 31 - 1
+_MAX_Q = 2 ** 30
+
+
+def _points_list(points, n_meshes, dev):
+    stacked = torch.is_tensor(points)
+    if stacked and (points.dim() != 3 or points.shape[2] != 3):
+        raise ValueError('closest_point: a stacked batch of points must be [B, n, 3], got %s' % (tuple(points.shape),))
+    pts = list(points)
+    if len(pts) != n_meshes:
+        raise ValueError('closest_point: %d point sets for %d meshes' % (len(pts), n_meshes))
+    for k, p in enumerate(pts):
+        if not torch.is_tensor(p) or p.dim() != 2 or p.shape[1] != 3:
+            raise ValueError('closest_point: points %d must be a [n, 3] tensor' % k)
+        if p.dtype != torch.float32:
+            raise ValueError('closest_point: points %d must be float32, got %s' % (k, p.dtype))
+        if p.device != dev:
+            raise ValueError('closest_point: points %d are not on the device of the meshes' % k)
+    return pts
+
+
+def closest_point(meshes, points, signed=False, bins=0, want_point=True):
+    """Exact nearest triangle of every point of ``points[b]`` on ``meshes[b]``, for all b in one call.
+
+    meshes: a list of B ``(verts [V, 3] fp32, faces [F, 3] int32)`` device tensors, in any frame.  points: a list of B
+    ``[n_b, 3]`` fp32 device tensors (ragged; a set may be empty) or one ``[B, n, 3]`` tensor.  Returns a list of B
+    ``(dist [n_b] fp32, face [n_b] int32, point [n_b, 3] fp32 or None)``:
+
+      dist   the distance to the nearest point of the nearest triangle: the minimum over all triangles of the fp64
+             expression ``mesh_to_sdf`` minimises, so at a lattice point it is that lattice's value, bit for bit.  With
+             ``signed`` it is negative where the ray towards -x crosses the surface an odd number of times (the rule of
+             ``mesh_to_sdf``: meaningful for a watertight mesh, the parity for an open one);
+      face   a triangle that attains it -- the lowest index among exact ties, which are the normal case along the
+             medial axis and outside a convex vertex or edge;
+      point  the closest point on that triangle (``want_point=False``: not computed, None).
+
+    A query with a non-finite coordinate gets NaN, -1, NaN and disturbs nothing else.  ``bins``: the size of the
+    culling grid per mesh, 1 .. 16, or 0 for the rule of include/ofx.h; it changes the time, never a bit of the
+    result, and neither does the order of the queries or the batch a mesh is in.  One host read, the status words.
+    Raises ValueError naming the mesh for a mesh without faces, a face index outside ``[0, V)`` or a non-finite vertex
+    used by a face; ValueError for wrong dtypes, shapes or ``bins`` before anything is launched."""
+    _lib.require_device()
+    bins = int(bins)
+    if not 0 <= bins <= MAX_BINS:
+        raise ValueError('closest_point: bins %d outside [0, %d]' % (bins, MAX_BINS))
+    meshes = mesh._check_meshes(meshes, 'closest_point')
+    if not meshes:
+        raise ValueError('closest_point: no meshes')
+    dev = meshes[0][0].device
+    for k, (v, f) in enumerate(meshes):
+        if f.shape[0] == 0 or v.shape[0] == 0:
+            raise ValueError('closest_point: shape %d has no faces' % k)
+        if v.device != dev:
+            raise ValueError('closest_point: shape %d is on another device' % k)
+    pts = _points_list(points, len(meshes), dev)
+    B = len(meshes)
+    nv = [int(v.shape[0]) for v, _ in meshes]
+    nf = [int(f.shape[0]) for _, f in meshes]
+    nq = [int(p.shape[0]) for p in pts]
+    Q = sum(nq)
+    if sum(nf) > _INT32_MAX or Q > _MAX_Q or B > 65535:
+        raise ValueError('closest_point: %d shapes, %d faces, %d queries exceed one call (65535, 2^31 - 1, 2^30)'
+                         % (B, sum(nf), Q))
+    verts, faces = mesh._cat(meshes)
+    q = pts[0].contiguous() if B == 1 else torch.cat(pts).contiguous()
+    offs = torch.from_numpy(np.stack([np.cumsum([0] + nv), np.cumsum([0] + nf),
+                                      np.cumsum([0] + nq)]).astype(np.int64)).to(dev)
+    nbytes = _lib.lib().ofx_mesh_query_ws_bytes(B, sum(nv), sum(nf), Q, bins)
+    if nbytes == 0:
+        raise ValueError('closest_point: %d shapes, %d vertices, %d faces, %d queries out of range'
+                         % (B, sum(nv), sum(nf), Q))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    dist = torch.empty(Q, dtype=torch.float32, device=dev)
+    face = torch.empty(Q, dtype=torch.int32, device=dev)
+    point = torch.empty(Q, 3, dtype=torch.float32, device=dev) if want_point else None
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    call('ofx_mesh_query', ptr(verts), ptr(faces), ptr(offs[0]), ptr(offs[1]), ptr(q) if Q else None, ptr(offs[2]), B,
+         Q, max(nq), bins, 1 if signed else 0, ptr(dist) if Q else None, ptr(face) if Q else None,
+         ptr(point) if want_point and Q else None, ptr(ws), ptr(status), stream())
+    bad = torch.nonzero(status).flatten().tolist()              # the host read
+    if bad:
+        raise ValueError('closest_point: shape %d has a face index outside [0, %d) or a non-finite vertex'
+                         % (bad[0], nv[bad[0]]))
+    ds, fs = dist.split(nq), face.split(nq)
+    ps = point.split(nq) if want_point else [None] * B
+    return [(ds[k], fs[k], ps[k]) for k in range(B)]
+
+
+def _dev_mesh(m, dev):
+    v, f = m
+    v = v if torch.is_tensor(v) else torch.from_numpy(np.ascontiguousarray(v, np.float32))
+    f = f if torch.is_tensor(f) else torch.from_numpy(np.ascontiguousarray(f, np.int64))
+    return (v.to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous(),
+            f.to(device=dev, dtype=torch.int32).reshape(-1, 3).contiguous())
+
+
+def mesh_error(a, b, n=100000, seed=0, signed=False):
+    """How far mesh ``a`` and mesh ``b`` (``(verts, faces)``, numpy or tensors, in one common frame) are apart: ``n``
+    points are drawn on each (``metrics.sample_surface(normalize=False)``, both with shape id 0) and measured EXACTLY
+    against the other's triangles, so only the sampled side carries sampling noise.  Returns a dict
+
+      a_to_b, b_to_a   each {'mean', 'rms', 'max'} of the distances of a's samples to b, of b's samples to a
+                       (``signed``: of the signed distances -- mean keeps the sign, rms and max use magnitudes --
+                       negative inside the other mesh, which must be watertight)
+      hausdorff        the larger of the two max
+      samples          n
+
+    Reductions run in float64 on the device; two host reads (the status words, the six numbers)."""
+    _lib.require_device()
+    dev = torch.device('cuda', torch.cuda.current_device())
+    ma, mb = _dev_mesh(a, dev), _dev_mesh(b, dev)
+    pts = metrics.sample_surface([ma, mb], n=int(n), seed=seed, normalize=False, ids=[0, 0])
+    res = closest_point([mb, ma], [pts[0].contiguous(), pts[1].contiguous()], signed=signed, want_point=False)
+    rows = []
+    for d, _, _ in res:
+        d = d.double()
+        rows.append(torch.stack([d.mean(), (d * d).mean().sqrt(), d.abs().max()]))
+    rows = torch.stack(rows).tolist()
+    keys = ('mean', 'rms', 'max')
+    return {'a_to_b': dict(zip(keys, rows[0])), 'b_to_a': dict(zip(keys, rows[1])),
+            'hausdorff': max(rows[0][2], rows[1][2]), 'samples': int(n)}
+
+
+def parser():
+    ap = argparse.ArgumentParser(prog='python -m octfusion_amd.mesh_query', description=__doc__.split('\n\n')[0])
+    ap.add_argument('--a', required=True, metavar='A.obj')
+    ap.add_argument('--b', required=True, metavar='B.obj')
+    ap.add_argument('--samples', type=int, default=100000, help='points drawn on each mesh')
+    ap.add_argument('--signed', action='store_true', help='signed distances (both meshes watertight)')
+    ap.add_argument('--seed', type=int, default=0)
+    return ap
+
+
+def main(argv=None):
+    args = parser().parse_args(argv)
+    _lib.require_device()
+    res = mesh_error(mesh.read_obj(args.a), mesh.read_obj(args.b), args.samples, args.seed, signed=args.signed)
+    print(json.dumps(res))
+    return res
+
+
+if __name__ == '__main__':
+    main()

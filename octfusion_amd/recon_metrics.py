@@ -104,7 +104,7 @@ def _oriented(sides, n, seed, dev):
     return out
 
 
-def surface_scores(gt, pred, n=100000, seed=0, thresholds=THRESHOLDS):
+def surface_scores(gt, pred, n=100000, seed=0, thresholds=THRESHOLDS, exact=False):
     """The surface half of the reconstruction table.  gt, pred: each a ``(verts, faces)`` mesh, of which n oriented
     surface points are drawn (metrics.sample_surface(normalize=False, normals=True), both sides with the same seed and
     shape id: a mesh against itself scores exactly 0), or a ``(points, normals)`` oriented cloud taken as it is; or
@@ -118,7 +118,12 @@ def surface_scores(gt, pred, n=100000, seed=0, thresholds=THRESHOLDS):
       recall, precision, fscore   share of gt / pred points with dist2 <= tau^2, and 2PR / (P + R) (0 when P + R == 0)
 
     The thresholds are in the clouds' own units; the defaults fit the [-0.5, 0.5] file frame.  All reductions run in
-    float64 on the device over the fp32 dist2 of ``nearest``; one host read.  A dict for one pair, a list for lists."""
+    float64 on the device over the fp32 dist2 of ``nearest``; one host read.  A dict for one pair, a list for lists.
+
+    exact: both sides must be meshes (ValueError otherwise).  The samples of each side are then measured against the
+    other side's TRIANGLES (mesh_query.closest_point) instead of its samples, so accuracy and completeness no longer
+    carry the sampling noise of the target side, and the normal compared is the unit normal of the nearest face (a
+    zero-area face has the zero normal).  One more host read, the status words of that call."""
     _lib.require_device()
     single = not isinstance(gt, list)
     gts, preds = ([gt], [pred]) if single else (gt, pred)
@@ -129,13 +134,28 @@ def surface_scores(gt, pred, n=100000, seed=0, thresholds=THRESHOLDS):
     G = _oriented(gts, n, seed, dev)
     P = _oriented(preds, n, seed, dev)
     N = len(G)
-    d2, ix = nearest([g[0] for g in G] + [p[0] for p in P], [p[0] for p in P] + [g[0] for g in G])
+    if exact:
+        if not all(_is_mesh(s) for s in list(gts) + list(preds)):
+            raise ValueError('surface_scores: exact=True needs a (verts, faces) mesh on both sides')
+        from . import mesh_query
+        targets = [mesh_query._dev_mesh(s, dev) for s in list(preds) + list(gts)]
+        hit = mesh_query.closest_point(targets, [g[0].contiguous() for g in G] + [p[0].contiguous() for p in P],
+                                       want_point=False)
+        d2 = [h[0] * h[0] for h in hit]
+        face_n = []
+        for (v, f), h in zip(targets, hit):
+            tri = v[f[h[1].long()].long()]                                    # [m, 3, 3]
+            face_n.append(torch.nn.functional.normalize(torch.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0],
+                                                                    dim=1), dim=1))
+    else:
+        d2, ix = nearest([g[0] for g in G] + [p[0] for p in P], [p[0] for p in P] + [g[0] for g in G])
     tau2 = torch.tensor([t * t for t in taus], dtype=torch.float64, device=dev)
     rows = []
     for k in range(2 * N):
         src, dst = (G[k], P[k]) if k < N else (P[k - N], G[k - N])
         d = d2[k].double()
-        dots = (src[1].double() * dst[1][ix[k].long()].double()).sum(1).abs()
+        other = face_n[k] if exact else dst[1][ix[k].long()]
+        dots = (src[1].double() * other.double()).sum(1).abs()
         within = (d[:, None] <= tau2[None, :]).double().mean(0)
         rows.append(torch.cat([torch.stack([d.sqrt().mean(), d.mean(), dots.mean()]), within]))
     rows = torch.stack(rows).tolist()                  # the one host read

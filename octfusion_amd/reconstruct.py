@@ -167,7 +167,7 @@ def _lap(timings, name, t0, device):
 def reconstruct(vae, cfg, inputs, device, sdf_resolution=256, sdf_scale=0.9, level=0.0, clean=False, batch=8, seed=0,
                 points=POINTS, chamfer_points=POINTS, fit=None, mpu_depth=None, out_dir=None, timings=None,
                 metrics=False, thresholds=recon_metrics.THRESHOLDS, occupancy=False, field_mesh=False, mesh_margin=1,
-                estimate_normals=False, normal_k=16):
+                estimate_normals=False, normal_k=16, exact=False):
     """Reconstruct every shape of ``inputs`` (read_inputs) through ``vae``, ``batch`` shapes per call.  cfg:
     recon_config(name), or a dict with depth, full_depth, point_scale.  points: samples per mesh input; fit: factor
     on the normalised mesh samples (default sdf_scale); mpu_depth: depth the SDF is read at (default depth_out);
@@ -178,7 +178,9 @@ def reconstruct(vae, cfg, inputs, device, sdf_resolution=256, sdf_scale=0.9, lev
     (file units), with chamfer_points samples per mesh side (POINTS when chamfer_points is 0, so that
     ``metrics=True, chamfer_points=0`` scores at 100 000 points without the single-block Chamfer launches); the gt side
     is the input mesh in the output frame or, for a point-cloud input, the oriented input cloud x point_scale cut to
-    that count by the Chamfer score's stride rule; ``null`` for an empty reconstruction.  occupancy: a point-cloud
+    that count by the Chamfer score's stride rule; ``null`` for an empty reconstruction.  exact: a mesh input is scored
+    with ``surface_scores(exact=True)``, samples against the other side's triangles (a point-cloud input has no
+    triangles and is scored as before).  occupancy: a point-cloud
     input whose directory holds ``points.npz`` gains ``iou``, ``iou_intersection``, ``iou_union`` =
     recon_metrics.occupancy_iou of the batch's ``neural_mpu`` field against that file; any other input gets ``null``
     and a warning; ``result['fields'][name]`` = (field, batch index).
@@ -276,7 +278,8 @@ def reconstruct(vae, cfg, inputs, device, sdf_resolution=256, sdf_scale=0.9, lev
                         pts, nrm = pts[sel], nrm[sel]
                     gt = (pts * ps, nrm)
                 shapes[it['name']]['scores'] = None if f.shape[0] == 0 else recon_metrics.surface_scores(
-                    gt, (v, f), n=score_points, seed=seed, thresholds=thresholds)
+                    gt, (v, f), n=score_points, seed=seed, thresholds=thresholds,
+                    exact=bool(exact) and gts[k] is not None)
             t0 = _lap(timings, 'scores', t0, device)
         if occupancy:
             for k, it in enumerate(group):
@@ -360,6 +363,9 @@ def parser():
                          '--chamfer-points samples per side (%d when that is 0)' % POINTS)
     ap.add_argument('--thresholds', type=float, nargs='+', default=list(recon_metrics.THRESHOLDS), metavar='T',
                     help='with --metrics: the F-score distance thresholds, in file units')
+    ap.add_argument('--exact', action='store_true',
+                    help='with --metrics: score a mesh input against the triangles of the other side instead of its '
+                         'samples (recon_metrics.surface_scores(exact=True), octfusion_amd.mesh_query)')
     ap.add_argument('--estimate-normals', action='store_true',
                     help='accept clouds without normals (pointcloud.npz without the key, bare .npy / .npz / .ply) and '
                          'estimate oriented normals on the device (octfusion_amd.normals)')
@@ -411,7 +417,7 @@ def main(argv=None):
                       chamfer_points=args.chamfer_points, fit=args.fit, mpu_depth=args.mpu_depth, out_dir=args.out,
                       timings=timings, metrics=args.metrics, thresholds=tuple(args.thresholds),
                       occupancy=args.occupancy, field_mesh=args.field_mesh, mesh_margin=args.mesh_margin,
-                      estimate_normals=args.estimate_normals, normal_k=args.normal_k)
+                      estimate_normals=args.estimate_normals, normal_k=args.normal_k, exact=args.exact)
     res.pop('meshes')
     res.pop('fields', None)
     print(json.dumps(res))

@@ -168,7 +168,12 @@ def main(argv=None):
     ap.add_argument('--cell-size', type=float, default=None, help='cell side, in the mesh\'s own units')
     ap.add_argument('--reg', type=float, default=1e-3)
     ap.add_argument('--clean', action='store_true', help='keep only the largest component of every mesh first')
+    ap.add_argument('--error', type=int, nargs='?', const=100000, default=None, metavar='N',
+                    help='add mesh_query.mesh_error(input, output, N) per mesh to the report: how far the surface '
+                         'moved, measured exactly against the triangles (N samples per side, default 100000)')
     args = ap.parse_args(argv)
+    if args.error is not None and args.error < 1:
+        raise ValueError('simplify: --error needs at least one sample')
     _check_args(args.cells, args.cell_size, args.reg)
     _lib.require_device()
     dev = torch.device('cuda', torch.cuda.current_device())
@@ -192,6 +197,10 @@ def main(argv=None):
            'vertices_in': [b[0] for b in before], 'faces_in': [b[1] for b in before],
            'vertices_out': [int(v.shape[0]) for v, _ in out], 'faces_out': [int(f.shape[0]) for _, f in out],
            'written': written, 'stats': stats['meshes']}
+    if args.error is not None:
+        from . import mesh_query
+        res['error'] = [mesh_query.mesh_error(m, o, args.error) if m[1].shape[0] and o[1].shape[0] else None
+                        for m, o in zip(meshes, out)]
     print(json.dumps(res))
     return res
 
