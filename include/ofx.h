@@ -1150,6 +1150,57 @@ int ofx_mesh_query(const float* verts, const int32_t* faces, const int64_t* vert
  * evaluated after the per-triangle box test (x 64 = point-triangle pairs).  NULL: counting off.  Sticky. */
 int ofx_mesh_query_set_counters(unsigned long long* words);
 
+/* ------------------------------------------------------------------ ray -> mesh casts (csrc/ofx_raycast.hip)
+ * The first hit of arbitrary rays on triangle meshes, exact and bit-reproducible: the sibling of ofx_mesh_query.
+ * tests/raycast_oracle.py restates the contract in float64.  Meshes concatenated as for ofx_mesh_query (verts, faces,
+ * vert_off, tri_off); rays org [Q, 3] and dir [Q, 3] fp32 with ray_off [batch + 1] (int64 device) = where each shape's
+ * rays begin, the last entry Q = total_q.  A shape may have zero rays.  max_q = the largest ray count of one shape.
+ * A point of the ray is org + t dir: t is in units of |dir|, which is not normalised.
+ *   The pair (ray, triangle), in fp64 with every operation rounded on its own (Woop, Benthin and Wald's watertight
+ *     test): kz = the axis of the largest |dir| (the lowest index among equals), kx, ky the next two in cyclic order,
+ *     swapped if dir[kz] < 0; Sx = dir[kx] / dir[kz], Sy = dir[ky] / dir[kz], Sz = 1 / dir[kz].  Per vertex P:
+ *     A = P - org, x = A[kx] - Sx A[kz], y = A[ky] - Sy A[kz], z = Sz A[kz] -- one expression of (ray, vertex).
+ *     U = det(Cx, By, Cy, Bx), V = det(Ax, Cy, Ay, Cx), W = det(Bx, Ay, By, Ax), det(a, b, c, d) = a b - c d with a
+ *     correct sign (Kahan's fma form).  The ray meets the triangle iff U, V, W are all >= 0 or all <= 0 (two-sided),
+ *     D = (U + V) + W != 0 (a triangle of zero area or seen edge-on never hits), and tmin <= (float)t <= tmax with
+ *     (float)t finite, where t = ((U Az + V Bz) + W Cz) / D.
+ *   t [Q] fp32  the minimum of t over ALL the shape's triangles the ray meets, rounded once; +inf for a miss.
+ *   face [Q] int32  the lowest index among the triangles whose t is that minimum as doubles; -1 for a miss.
+ *   point [Q, 3] fp32 (may be NULL)  ((U a + V b) + W c) / D of the winning face's original vertices a, b, c.
+ *   cosn [Q] fp32 (may be NULL)  n . dir / (|n| |dir|), n = (b - a) x (c - a): negative where the ray meets the face
+ *     from its front.  A miss gets NaN in point and cosn.
+ *   A ray with a non-finite component or a zero direction gets t = +inf, face = -1, point = cosn = NaN and changes no
+ *   other ray's result.
+ *   status [batch], bins: as for ofx_mesh_query (same conditions, same grid rule; a shape with a non-zero status
+ *     has its outputs left unwritten).  coherent != 0: consecutive rays are neighbours already (camera rays in 8 x 8
+ *     pixel tiles) and are not sorted; else rays are ordered by shape, Morton code of the origin and octant of the
+ *     direction.  tmin, tmax: not NaN; infinities are allowed.
+ *   The output is a pure function of the inputs, bitwise: the same alone or in a batch, for any order of the rays, any
+ *   bins and either value of coherent (they only decide what is skipped; every skip is a slab test of an inflated box,
+ *   DESIGN.md 4.20).  ws: ofx_ray_cast_ws_bytes (0 for arguments out of range, the ranges of ofx_mesh_query_ws_bytes).
+ *   Bad arguments: OFX_EINVAL, nothing launched. */
+size_t ofx_ray_cast_ws_bytes(int batch, int64_t total_verts, int64_t total_faces, int64_t total_q, int bins);
+int ofx_ray_cast(const float* verts, const int32_t* faces, const int64_t* vert_off, const int64_t* tri_off,
+                 const float* org, const float* dir, const int64_t* ray_off, int batch, int64_t total_q, int64_t max_q,
+                 float tmin, float tmax, int bins, int coherent, float* t, int32_t* face, float* point, float* cosn,
+                 void* ws, int32_t* status, void* stream);
+/* Measurement aid (tools/raycast_probe.py; not on the operator path), as ofx_mesh_query_set_counters: per wave of 64
+ * rays words[0] += bins visited (at least one lane passed the bin's slab test), words[1] += triangles staged,
+ * words[2] += (ray, triangle) pairs evaluated after the per-triangle slab test.  NULL: counting off.  Sticky. */
+int ofx_ray_cast_set_counters(unsigned long long* words);
+/* The hits of a cast as an oriented point cloud, compacted in ray order (ballots and a scan over block counts, never
+ * atomics): for every ray with face >= 0, points = org + (t + sigma g / |dir|) dir with g a standard normal from the
+ * counter hash (ofx_metrics_hash's chain over seed, shape, the ray's index within its shape, draws 0 and 1; Box-Muller
+ * in fp64; sigma == 0: no noise), normals = the hit face's unit normal turned against the ray.  out_off [batch + 1]
+ * (int64 device): where each shape's points begin, the last entry the number of hits.  points / normals have room for
+ * total_q rows.  t and face are the outputs of ofx_ray_cast on the same meshes and rays; a face index out of range
+ * gives NaN rows.  ws: ofx_ray_scan_ws_bytes (0 for total_q outside [0, 2^30]). */
+size_t ofx_ray_scan_ws_bytes(int64_t total_q);
+int ofx_ray_scan(const float* verts, const int32_t* faces, const int64_t* vert_off, const int64_t* tri_off,
+                 const float* org, const float* dir, const int64_t* ray_off, int batch, int64_t total_q, const float* t,
+                 const int32_t* face, float sigma, uint64_t seed, float* points, float* normals, int64_t* out_off,
+                 void* ws, void* stream);
+
 /* ------------------------------------------------------------------ rendering (csrc/ofx_render.hip)
  * Shaded views of triangle meshes for the reference's FID image sets (utils/render_utils.py:14-23, utils/render/):
  * a deterministic renderer of the project's own, parity with pyrender unpinned; tests/render_oracle.py

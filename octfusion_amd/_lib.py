@@ -223,6 +223,13 @@ _SIGS = {
     'ofx_mesh_query': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_l, c_l, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p],
                        True),
     'ofx_mesh_query_set_counters': (c_i, [c_p], True),
+    'ofx_ray_cast_ws_bytes': (c_sz, [c_i, c_l, c_l, c_l, c_i], False),
+    'ofx_ray_cast': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_l, c_l, c_f, c_f, c_i, c_i, c_p, c_p, c_p, c_p, c_p,
+                           c_p, c_p], True),
+    'ofx_ray_cast_set_counters': (c_i, [c_p], True),
+    'ofx_ray_scan_ws_bytes': (c_sz, [c_l], False),
+    'ofx_ray_scan': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_l, c_p, c_p, c_f, c_u64, c_p, c_p, c_p, c_p, c_p],
+                     True),
     'ofx_render_project': (c_i, [c_p, c_p, c_i, c_l, c_l, c_p, c_i, c_i, c_d, c_d, c_d, c_i, c_p, c_p, c_p, c_p], True),
     'ofx_render_raster_ws_bytes': (c_sz, [c_i, c_l], False),
     'ofx_render_raster': (c_i, [c_p, c_p, c_i, c_l, c_l, c_l, c_i, c_i, c_p, c_p, c_l, c_p, c_p, c_p, c_p], True),
