@@ -2,11 +2,9 @@
 // search of ofx_mesh2sdf.hip lifted off the lattice.  Contract: include/ofx.h; tests/meshquery_oracle.py restates it in
 // float64 (brute force, Ericson's regions).  DESIGN.md section 4.19 has the exactness argument and the figures.
 //
-//   bins   every valid triangle goes into ONE bin of a G^3 grid over the shape's OWN bounding box (of the vertices its
-//          valid faces use) by its clamped centroid; a bin keeps the exact bounding box of its triangles.  G is given
-//          or comes from the shape's face count (mq_bins).  bound -> count -> ofx_scan_i32 -> fill; the fill copies
-//          the nine coordinates and the face's index into bin order.  Nothing below depends on which bin a triangle
-//          is in or on the order inside a bin.
+//   bins   the per-shape G^3 centroid bins of ofx_tribins.h, built by ofx_tribins_build: the structure the ray casts
+//          search too.  G is given or comes from the shape's face count (tb_bins).  Nothing below depends on which
+//          bin a triangle is in or on the order inside a bin.
 //   order  a key per query: shape << 32 | non-finite << 30 | 30-bit Morton code of the query clamped into the shape's
 //          box; ofx_points_sort orders them, so a wave gets 64 neighbouring queries.  Where the Morton order jumps
 //          across the shape inside a wave, the wave is searched as two parts (mq_split).  Performance devices only.
@@ -20,7 +18,7 @@
 //   sign   the same waves.  A bin or triangle is a candidate iff its yz-box meets K's yz-box and its lowest x is <= K's
 //          highest x; a crossing counts iff x_cross <= (double)q.x; the parity is one bit in a register per lane.  The
 //          edge functions, the tie rule and x_cross are the lattice entry's (ms_edge, ms_cross_x).
-#include "ofx_common.h"
+#include "ofx_tribins.h"
 
 #include <cmath>
 
@@ -30,183 +28,17 @@
 
 namespace {
 
-constexpr int MQ_MAX_G = 16;       // at most 16^3 bins per shape
-constexpr int MQ_PREP_T = 256;
-constexpr int MQ_W = 10;           // words per binned triangle: nine coordinates and the face's index
-constexpr int MQ_FACES_PER_G2 = 256;
-
-// The automatic grid: the smallest G in 1 .. 16 with 256 G^2 >= F.  A surface meets about 3 G^2 of the G^3 bins, so
-// an occupied bin holds about F / (3 G^2) <= 85 triangles: one or two staging rounds of 64.
-__host__ __device__ inline int mq_bins(int64_t F, int bins) {
-  if (bins) return bins;
-  int g = 1;
-  while (g < MQ_MAX_G && (int64_t)MQ_FACES_PER_G2 * g * g < F) ++g;
-  return g;
-}
-// bins of one shape in the workspace (the stride of the per-bin arrays)
-inline int mq_stride(int bins) { return bins ? bins * bins * bins : MQ_MAX_G * MQ_MAX_G * MQ_MAX_G; }
-
-struct MqWs {
-  int32_t* cnt;      // [batch * GS]      triangles per bin
-  int32_t* off;      // [batch * GS + 1]  exclusive scan
-  int32_t* cursor;   // [batch * GS]      fill cursors
-  int32_t* box;      // [batch * GS * 6]  keys of min xyz, max xyz of a bin
-  int32_t* sbox;     // [batch * 6]       the same of a shape
-  void* scan_ws;
-  int64_t* key;      // [Q] sort keys, [Q] sorted
-  int64_t* skey;
-  int32_t* idx;      // [Q] query index, [Q] sorted
-  int32_t* sidx;
-  void* sort_ws;
-  size_t sort_bytes;
-  float* tri;        // [total_faces * 10] records in bin order (last: the only array sized by the faces)
-};
-
-inline size_t mq_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
-size_t mq_layout(int batch, int64_t total_faces, int64_t total_q, int bins, char* base, MqWs* w) {
-  const int64_t nb = (int64_t)batch * mq_stride(bins);
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    char* p = base ? base + o : nullptr;
-    o += mq_align(bytes);
-    return p;
-  };
-  MqWs l;
-  l.cnt = (int32_t*)take(nb * sizeof(int32_t));
-  l.off = (int32_t*)take((nb + 1) * sizeof(int32_t));
-  l.cursor = (int32_t*)take(nb * sizeof(int32_t));
-  l.box = (int32_t*)take(nb * 6 * sizeof(int32_t));
-  l.sbox = (int32_t*)take((size_t)batch * 6 * sizeof(int32_t));
-  l.scan_ws = take(ofx_scan_ws_bytes(nb));
-  l.key = (int64_t*)take((size_t)total_q * sizeof(int64_t));
-  l.skey = (int64_t*)take((size_t)total_q * sizeof(int64_t));
-  l.idx = (int32_t*)take((size_t)total_q * sizeof(int32_t));
-  l.sidx = (int32_t*)take((size_t)total_q * sizeof(int32_t));
-  l.sort_bytes = ofx_points_sort_ws_bytes(total_q);
-  l.sort_ws = take(l.sort_bytes);
-  l.tri = (float*)take((size_t)total_faces * MQ_W * sizeof(float));
-  if (w) *w = l;
-  return o;
-}
-
-struct MqMesh {
-  const float* verts;
-  const int32_t* faces;
-  const int64_t* vert_off;
-  const int64_t* tri_off;
+// the meshes of a call and its queries
+struct MqMesh : TbMesh {
   const float* q;
   const int64_t* q_off;
-  int batch, bins, GS;
 };
-
-__device__ __forceinline__ int mq_G(const MqMesh& m, int b) {
-  return mq_bins(m.tri_off[b + 1] - m.tri_off[b], m.bins);
-}
-
-__global__ __launch_bounds__(MQ_PREP_T) void mq_init_kernel(int64_t nb, MqWs w, int batch,
-                                                            int32_t* __restrict__ status) {
-  const int64_t stride = (int64_t)gridDim.x * MQ_PREP_T;
-  for (int64_t i = (int64_t)blockIdx.x * MQ_PREP_T + threadIdx.x; i < nb; i += stride) {
-    w.cnt[i] = 0;
-    w.cursor[i] = 0;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      w.box[i * 6 + a] = INT32_MAX;
-      w.box[i * 6 + 3 + a] = INT32_MIN;
-    }
-    if (i < batch) {
-      status[i] = 0;
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        w.sbox[i * 6 + a] = INT32_MAX;
-        w.sbox[i * 6 + 3 + a] = INT32_MIN;
-      }
-    }
-  }
-}
-
-// Bin of a triangle: its centroid in the G^3 grid over the shape's box (a box without extent on an axis: cell 0).
-__device__ __forceinline__ int mq_bin_of(const int32_t* __restrict__ sbox, int b, int G, const float (&c)[9]) {
-  int g[3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const double lo = (double)ms_unkey(sbox[b * 6 + a]), ext = (double)ms_unkey(sbox[b * 6 + 3 + a]) - lo;
-    const double mid = ((double)c[a] + (double)c[3 + a] + (double)c[6 + a]) * (1.0 / 3.0);
-    double f = ext > 0.0 ? floor((mid - lo) / ext * (double)G) : 0.0;
-    f = f >= 0.0 ? f : 0.0;                       // written so that a NaN (an overflowing extent) lands in cell 0
-    f = f > (double)(G - 1) ? (double)(G - 1) : f;
-    g[a] = (int)f;
-  }
-  return (g[0] * G + g[1]) * G + g[2];
-}
-
-// Validate every triangle and bound its shape (min / max on order-preserving keys).  A wave whose triangles all belong
-// to one shape reduces its box first: one set of atomics per wave, not per triangle.
-__global__ __launch_bounds__(MQ_PREP_T) void mq_bound_kernel(MqMesh m, MqWs w, int32_t* __restrict__ status) {
-  const int64_t total = m.tri_off[m.batch];
-  const int64_t stride = (int64_t)gridDim.x * MQ_PREP_T;
-  for (int64_t t0 = (int64_t)blockIdx.x * MQ_PREP_T; t0 < total; t0 += stride) {      // uniform in a block
-    const int64_t t = t0 + threadIdx.x;
-    const int b = ms_shape_of(m.tri_off, m.batch, t < total ? t : total - 1);
-    float c[9], lo[3], hi[3];
-    const bool in = t < total;
-    const bool ok = in && ms_load(m.verts, m.faces, m.vert_off, t, b, c);
-    if (in && !ok) atomicOr(&status[b], 1);
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      lo[a] = ok ? fminf(fminf(c[a], c[3 + a]), c[6 + a]) : INFINITY;
-      hi[a] = ok ? fmaxf(fmaxf(c[a], c[3 + a]), c[6 + a]) : -INFINITY;
-    }
-    const bool one = __shfl(b, 0) == __shfl(b, MS_T - 1);        // shapes are non-decreasing along t
-    if (one) {
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        lo[a] = ms_wave_min(lo[a]);
-        hi[a] = ms_wave_max(hi[a]);
-      }
-    }
-    if (one ? ((threadIdx.x & (MS_T - 1)) == 0 && lo[0] <= hi[0]) : ok) {
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        atomicMin(&w.sbox[b * 6 + a], ms_key(lo[a]));
-        atomicMax(&w.sbox[b * 6 + 3 + a], ms_key(hi[a]));
-      }
-    }
-  }
-}
-
-// STEP 1: count and bound the bins; 2: copy the records into bin order.
-template <int STEP>
-__global__ __launch_bounds__(MQ_PREP_T) void mq_bin_kernel(MqMesh m, MqWs w) {
-  const int64_t total = m.tri_off[m.batch];
-  const int64_t stride = (int64_t)gridDim.x * MQ_PREP_T;
-  for (int64_t t = (int64_t)blockIdx.x * MQ_PREP_T + threadIdx.x; t < total; t += stride) {
-    const int b = ms_shape_of(m.tri_off, m.batch, t);
-    float c[9];
-    if (!ms_load(m.verts, m.faces, m.vert_off, t, b, c)) continue;      // mq_bound_kernel has set the status
-    const int64_t bin = (int64_t)b * m.GS + mq_bin_of(w.sbox, b, mq_G(m, b), c);
-    if (STEP == 1) {
-      atomicAdd(&w.cnt[bin], 1);
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        atomicMin(&w.box[bin * 6 + a], ms_key(fminf(fminf(c[a], c[3 + a]), c[6 + a])));
-        atomicMax(&w.box[bin * 6 + 3 + a], ms_key(fmaxf(fmaxf(c[a], c[3 + a]), c[6 + a])));
-      }
-    } else {
-      const int64_t slot = (int64_t)w.off[bin] + atomicAdd(&w.cursor[bin], 1);
-#pragma unroll
-      for (int k = 0; k < 9; ++k) w.tri[slot * MQ_W + k] = c[k];
-      w.tri[slot * MQ_W + 9] = __int_as_float((int32_t)(t - m.tri_off[b]));
-    }
-  }
-}
 
 // Sort key of every query: shape << 32 | non-finite << 30 | Morton code of the query in a 1024^3 grid over the shape's
 // box.  Only the shape bits matter for the result (a shape's queries stay in its range of sorted positions).
-__global__ __launch_bounds__(MQ_PREP_T) void mq_key_kernel(MqMesh m, MqWs w, int64_t total_q) {
-  const int64_t stride = (int64_t)gridDim.x * MQ_PREP_T;
-  for (int64_t i = (int64_t)blockIdx.x * MQ_PREP_T + threadIdx.x; i < total_q; i += stride) {
+__global__ __launch_bounds__(TB_PREP_T) void mq_key_kernel(MqMesh m, TbBins w, TbOrder o, int64_t total_q) {
+  const int64_t stride = (int64_t)gridDim.x * TB_PREP_T;
+  for (int64_t i = (int64_t)blockIdx.x * TB_PREP_T + threadIdx.x; i < total_q; i += stride) {
     const int b = ms_shape_of(m.q_off, m.batch, i);
     uint64_t code = 0;
     bool fin = true;
@@ -220,8 +52,8 @@ __global__ __launch_bounds__(MQ_PREP_T) void mq_key_kernel(MqMesh m, MqWs w, int
       cell[a] = f >= 0.f ? (f < 1023.f ? (int)f : 1023) : 0;      // a NaN lands in cell 0
     }
     code = fin ? ofx_xyz2morton(cell[0], cell[1], cell[2]) : (1ull << 30);
-    w.key[i] = (int64_t)(((uint64_t)b << 32) | code);
-    w.idx[i] = (int32_t)i;
+    o.key[i] = (int64_t)(((uint64_t)b << 32) | code);
+    o.idx[i] = (int32_t)i;
   }
 }
 
@@ -284,9 +116,10 @@ __device__ __forceinline__ int mq_split(bool fin, const float (&qf)[3], int lane
 }
 
 template <bool COUNT>
-__global__ __launch_bounds__(MS_T) void mq_dist_kernel(MqMesh m, MqWs w, const int32_t* __restrict__ status,
-                                                       float* __restrict__ dist, int32_t* __restrict__ face,
-                                                       float* __restrict__ point, unsigned long long* counters) {
+__global__ __launch_bounds__(MS_T) void mq_dist_kernel(MqMesh m, TbBins w, TbOrder o,
+                                                       const int32_t* __restrict__ status, float* __restrict__ dist,
+                                                       int32_t* __restrict__ face, float* __restrict__ point,
+                                                       unsigned long long* counters) {
   __shared__ double rec[MS_REC * MS_T];
   __shared__ int32_t ids[MS_T];
   uint32_t tally[3] = {0u, 0u, 0u};            // bins searched, triangles staged, triangles evaluated (per wave)
@@ -297,14 +130,14 @@ __global__ __launch_bounds__(MS_T) void mq_dist_kernel(MqMesh m, MqWs w, const i
   int64_t qi;
   bool fin;
   float qf[3];
-  mq_wave(m, w.sidx, b, lane, qi, fin, qf);
+  mq_wave(m, o.sidx, b, lane, qi, fin, qf);
   if (qi >= 0 && !fin) {                        // a non-finite query: NaN, -1, NaN
     dist[qi] = NAN;
     face[qi] = -1;
     if (point) point[qi * 3] = point[qi * 3 + 1] = point[qi * 3 + 2] = NAN;
   }
   const int split = mq_split(fin, qf, lane);
-  const int G = mq_G(m, b), G3 = G * G * G;
+  const int G = tb_G(m, b), G3 = G * G * G;
   const int64_t bin0 = (int64_t)b * m.GS;
 #pragma unroll 1
   for (int part = 0; part < 2; ++part) {
@@ -392,8 +225,8 @@ __global__ __launch_bounds__(MS_T) void mq_dist_kernel(MqMesh m, MqWs w, const i
   if (COUNT && lane < 3) atomicAdd(&counters[lane], (unsigned long long)tally[lane]);
 }
 
-__global__ __launch_bounds__(MS_T) void mq_sign_kernel(MqMesh m, MqWs w, const int32_t* __restrict__ status,
-                                                       float* __restrict__ dist) {
+__global__ __launch_bounds__(MS_T) void mq_sign_kernel(MqMesh m, TbBins w, TbOrder o,
+                                                       const int32_t* __restrict__ status, float* __restrict__ dist) {
   __shared__ double rec[MS_REC * MS_T];
   const int b = blockIdx.y;
   if (status[b]) return;
@@ -402,9 +235,9 @@ __global__ __launch_bounds__(MS_T) void mq_sign_kernel(MqMesh m, MqWs w, const i
   int64_t qi;
   bool fin;
   float qf[3];
-  mq_wave(m, w.sidx, b, lane, qi, fin, qf);
+  mq_wave(m, o.sidx, b, lane, qi, fin, qf);
   const int split = mq_split(fin, qf, lane);
-  const int G = mq_G(m, b), G3 = G * G * G;
+  const int G = tb_G(m, b), G3 = G * G * G;
   const int64_t bin0 = (int64_t)b * m.GS;
 #pragma unroll 1
   for (int part = 0; part < 2; ++part) {
@@ -438,7 +271,7 @@ __global__ __launch_bounds__(MS_T) void mq_sign_kernel(MqMesh m, MqWs w, const i
           if (keep) {
             float c[9];
 #pragma unroll
-            for (int q = 0; q < 9; ++q) c[q] = w.tri[(start + t) * MQ_W + q];
+            for (int q = 0; q < 9; ++q) c[q] = w.tri[(start + t) * TB_W + q];
             const double y0 = c[1], z0 = c[2], y1 = c[4], z1 = c[5], y2 = c[7], z2 = c[8];
             keep = fmin(fmin(y0, y1), y2) <= yhi && fmax(fmax(y0, y1), y2) >= ylo &&
                    fmin(fmin(z0, z1), z2) <= zhi && fmax(fmax(z0, z1), z2) >= zlo &&
@@ -481,17 +314,12 @@ __global__ __launch_bounds__(MS_T) void mq_sign_kernel(MqMesh m, MqWs w, const i
 
 unsigned long long* mq_counters = nullptr;      // ofx_mesh_query_set_counters
 
-bool mq_valid(int batch, int64_t total_verts, int64_t total_faces, int64_t total_q, int bins) {
-  return batch >= 1 && batch <= 65535 && total_verts >= 1 && total_faces >= 1 && total_faces <= INT32_MAX &&
-         total_q >= 0 && total_q <= (int64_t(1) << 30) && bins >= 0 && bins <= MQ_MAX_G;
-}
-
 }  // namespace
 
 extern "C" size_t ofx_mesh_query_ws_bytes(int batch, int64_t total_verts, int64_t total_faces, int64_t total_q,
                                           int bins) {
-  if (!mq_valid(batch, total_verts, total_faces, total_q, bins)) return 0;
-  return mq_layout(batch, total_faces, total_q, bins, nullptr, nullptr);
+  if (!ofx_tribins_args_ok(batch, total_verts, total_faces, total_q, bins)) return 0;
+  return ofx_tribins_layout(batch, total_faces, total_q, bins, nullptr, nullptr, nullptr);
 }
 
 extern "C" int ofx_mesh_query_set_counters(unsigned long long* words) {
@@ -503,37 +331,27 @@ extern "C" int ofx_mesh_query(const float* verts, const int32_t* faces, const in
                               const float* q, const int64_t* q_off, int batch, int64_t total_q, int64_t max_q,
                               int bins, int signed_, float* dist, int32_t* face, float* point, void* ws,
                               int32_t* status, void* stream) {
-  if (!verts || !faces || !vert_off || !tri_off || !q_off || !ws || !status || !mq_valid(batch, 1, 1, total_q, bins) ||
-      max_q < 0 || max_q > total_q || (total_q > 0 && (!q || !dist || !face || max_q < 1)))
+  if (!verts || !faces || !vert_off || !tri_off || !q_off || !ws || !status ||
+      !ofx_tribins_args_ok(batch, 1, 1, total_q, bins) || max_q < 0 || max_q > total_q ||
+      (total_q > 0 && (!q || !dist || !face || max_q < 1)))
     return OFX_EINVAL;
   hipStream_t st = ofx_stream(stream);
-  const int GS = mq_stride(bins);
-  const int64_t nb = (int64_t)batch * GS;
-  MqWs w;
-  mq_layout(batch, 0, total_q, bins, (char*)ws, &w);   // the face-sized array is the last one: its size is not needed
-  const MqMesh m{verts, faces, vert_off, tri_off, q, q_off, batch, bins, GS};
-  mq_init_kernel<<<ofx_grid(nb, MQ_PREP_T), MQ_PREP_T, 0, st>>>(nb, w, batch, status);
+  TbBins w;
+  TbOrder o;
+  ofx_tribins_layout(batch, 0, total_q, bins, (char*)ws, &w, &o);   // the records are last: their size is not needed
+  const MqMesh m{{verts, faces, vert_off, tri_off, batch, bins, tb_stride(bins)}, q, q_off};
+  int rc = ofx_tribins_build(m, w, total_q, status, stream);
+  if (rc || total_q == 0) return rc;              // no queries: the status words are still written
+  mq_key_kernel<<<ofx_grid(total_q, TB_PREP_T), TB_PREP_T, 0, st>>>(m, w, o, total_q);
   OFX_LAUNCH_CHECK();
-  const int prep = 2048;                          // grid-stride: the face count lives on the device
-  mq_bound_kernel<<<prep, MQ_PREP_T, 0, st>>>(m, w, status);
-  OFX_LAUNCH_CHECK();
-  if (total_q == 0) return OFX_OK;                // the status words are still written
-  mq_bin_kernel<1><<<prep, MQ_PREP_T, 0, st>>>(m, w);
-  OFX_LAUNCH_CHECK();
-  int rc = ofx_scan_i32(w.cnt, w.off, nb, w.scan_ws, stream);
-  if (rc) return rc;
-  mq_bin_kernel<2><<<prep, MQ_PREP_T, 0, st>>>(m, w);
-  OFX_LAUNCH_CHECK();
-  mq_key_kernel<<<ofx_grid(total_q, MQ_PREP_T), MQ_PREP_T, 0, st>>>(m, w, total_q);
-  OFX_LAUNCH_CHECK();
-  rc = ofx_points_sort(w.key, w.idx, total_q, w.skey, w.sidx, w.sort_ws, w.sort_bytes, stream);
+  rc = ofx_points_sort(o.key, o.idx, total_q, o.skey, o.sidx, o.sort_ws, o.sort_bytes, stream);
   if (rc) return rc;
   const dim3 waves((unsigned)ofx_cdiv(max_q, MS_T), (unsigned)batch);
-  if (mq_counters) mq_dist_kernel<true><<<waves, MS_T, 0, st>>>(m, w, status, dist, face, point, mq_counters);
-  else mq_dist_kernel<false><<<waves, MS_T, 0, st>>>(m, w, status, dist, face, point, nullptr);
+  if (mq_counters) mq_dist_kernel<true><<<waves, MS_T, 0, st>>>(m, w, o, status, dist, face, point, mq_counters);
+  else mq_dist_kernel<false><<<waves, MS_T, 0, st>>>(m, w, o, status, dist, face, point, nullptr);
   OFX_LAUNCH_CHECK();
   if (signed_) {
-    mq_sign_kernel<<<waves, MS_T, 0, st>>>(m, w, status, dist);
+    mq_sign_kernel<<<waves, MS_T, 0, st>>>(m, w, o, status, dist);
     OFX_LAUNCH_CHECK();
   }
   return OFX_OK;

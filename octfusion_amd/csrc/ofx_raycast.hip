@@ -2,10 +2,9 @@
 // the sibling of the point queries of ofx_meshquery.hip.  Contract: include/ofx.h; tests/raycast_oracle.py restates it in
 // float64 (brute force).  DESIGN.md section 4.20 has the exactness argument and the figures.
 //
-//   bins   the per-shape G^3 centroid bins of section 4.19, built by the same rule (rc_bins = the query entry's
-//          automatic grid; bound -> count -> ofx_scan_i32 -> fill, a record = nine coordinates and the face's index).
-//          The kernels are restated here rather than shared so that nothing the lattice and query entries run is
-//          touched.  Nothing below depends on which bin a triangle is in or on the order inside a bin.
+//   bins   the per-shape G^3 centroid bins of ofx_tribins.h, built by ofx_tribins_build: the structure the point
+//          queries search (section 4.19).  Nothing below depends on which bin a triangle is in or on the order inside
+//          a bin.
 //   order  a key per ray: shape << 32 | invalid << 30 | 27-bit Morton code of the origin clamped into the shape's box
 //          << 3 | octant of the direction; ofx_points_sort (stable) orders them, so a wave gets 64 neighbouring rays.
 //          `coherent` != 0: the caller's order is kept (camera rays in 8 x 8 pixel tiles).  A performance device only.
@@ -20,7 +19,7 @@
 //          winning face's original vertices.
 //   scan   ofx_ray_scan: the hits of a cast, compacted in ray order (ballot + ofx_scan_i32 over block counts) into an
 //          oriented point cloud, optionally with Gaussian noise along the ray from the counter hash.
-#include "ofx_common.h"
+#include "ofx_tribins.h"
 
 #include <cmath>
 
@@ -30,177 +29,15 @@
 
 namespace {
 
-constexpr int RC_MAX_G = 16;       // at most 16^3 bins per shape
-constexpr int RC_PREP_T = 256;
-constexpr int RC_W = 10;           // words per binned triangle: nine coordinates and the face's index
-constexpr int RC_FACES_PER_G2 = 256;
 constexpr float RC_REL = 1.0e-5f;  // every box is inflated by RC_REL * (largest |bound| + |origin|) per axis before a skip
 constexpr float RC_DMIN = 0x1p-100f, RC_DMAX = 0x1p100f;      // a direction component outside: the ray is never culled
 
-// the automatic grid of the query entry (section 4.19): the smallest G in 1 .. 16 with 256 G^2 >= F
-__host__ __device__ inline int rc_bins(int64_t F, int bins) {
-  if (bins) return bins;
-  int g = 1;
-  while (g < RC_MAX_G && (int64_t)RC_FACES_PER_G2 * g * g < F) ++g;
-  return g;
-}
-inline int rc_stride(int bins) { return bins ? bins * bins * bins : RC_MAX_G * RC_MAX_G * RC_MAX_G; }
-
-struct RcWs {
-  int32_t* cnt;      // [batch * GS]      triangles per bin
-  int32_t* off;      // [batch * GS + 1]  exclusive scan
-  int32_t* cursor;   // [batch * GS]      fill cursors
-  int32_t* box;      // [batch * GS * 6]  keys of min xyz, max xyz of a bin
-  int32_t* sbox;     // [batch * 6]       the same of a shape
-  void* scan_ws;
-  int64_t* key;      // [Q] sort keys, [Q] sorted
-  int64_t* skey;
-  int32_t* idx;      // [Q] ray index, [Q] sorted
-  int32_t* sidx;
-  void* sort_ws;
-  size_t sort_bytes;
-  float* tri;        // [total_faces * 10] records in bin order (last: the only array sized by the faces)
-};
-
-inline size_t rc_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
-size_t rc_layout(int batch, int64_t total_faces, int64_t total_q, int bins, char* base, RcWs* w) {
-  const int64_t nb = (int64_t)batch * rc_stride(bins);
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    char* p = base ? base + o : nullptr;
-    o += rc_align(bytes);
-    return p;
-  };
-  RcWs l;
-  l.cnt = (int32_t*)take(nb * sizeof(int32_t));
-  l.off = (int32_t*)take((nb + 1) * sizeof(int32_t));
-  l.cursor = (int32_t*)take(nb * sizeof(int32_t));
-  l.box = (int32_t*)take(nb * 6 * sizeof(int32_t));
-  l.sbox = (int32_t*)take((size_t)batch * 6 * sizeof(int32_t));
-  l.scan_ws = take(ofx_scan_ws_bytes(nb));
-  l.key = (int64_t*)take((size_t)total_q * sizeof(int64_t));
-  l.skey = (int64_t*)take((size_t)total_q * sizeof(int64_t));
-  l.idx = (int32_t*)take((size_t)total_q * sizeof(int32_t));
-  l.sidx = (int32_t*)take((size_t)total_q * sizeof(int32_t));
-  l.sort_bytes = ofx_points_sort_ws_bytes(total_q);
-  l.sort_ws = take(l.sort_bytes);
-  l.tri = (float*)take((size_t)total_faces * RC_W * sizeof(float));
-  if (w) *w = l;
-  return o;
-}
-
-struct RcMesh {
-  const float* verts;
-  const int32_t* faces;
-  const int64_t* vert_off;
-  const int64_t* tri_off;
+// the meshes of a call and its rays
+struct RcMesh : TbMesh {
   const float* org;
   const float* dir;
   const int64_t* ray_off;
-  int batch, bins, GS;
 };
-
-__device__ __forceinline__ int rc_G(const RcMesh& m, int b) { return rc_bins(m.tri_off[b + 1] - m.tri_off[b], m.bins); }
-
-// ---- the bins (section 4.19's, restated) --------------------------------------------------------------------------
-__global__ __launch_bounds__(RC_PREP_T) void rc_init_kernel(int64_t nb, RcWs w, int batch,
-                                                            int32_t* __restrict__ status) {
-  const int64_t stride = (int64_t)gridDim.x * RC_PREP_T;
-  for (int64_t i = (int64_t)blockIdx.x * RC_PREP_T + threadIdx.x; i < nb; i += stride) {
-    w.cnt[i] = 0;
-    w.cursor[i] = 0;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      w.box[i * 6 + a] = INT32_MAX;
-      w.box[i * 6 + 3 + a] = INT32_MIN;
-    }
-    if (i < batch) {
-      status[i] = 0;
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        w.sbox[i * 6 + a] = INT32_MAX;
-        w.sbox[i * 6 + 3 + a] = INT32_MIN;
-      }
-    }
-  }
-}
-
-// Bin of a triangle: its centroid in the G^3 grid over the shape's box (a box without extent on an axis: cell 0).
-__device__ __forceinline__ int rc_bin_of(const int32_t* __restrict__ sbox, int b, int G, const float (&c)[9]) {
-  int g[3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const double lo = (double)ms_unkey(sbox[b * 6 + a]), ext = (double)ms_unkey(sbox[b * 6 + 3 + a]) - lo;
-    const double mid = ((double)c[a] + (double)c[3 + a] + (double)c[6 + a]) * (1.0 / 3.0);
-    double f = ext > 0.0 ? floor((mid - lo) / ext * (double)G) : 0.0;
-    f = f >= 0.0 ? f : 0.0;                       // written so that a NaN (an overflowing extent) lands in cell 0
-    f = f > (double)(G - 1) ? (double)(G - 1) : f;
-    g[a] = (int)f;
-  }
-  return (g[0] * G + g[1]) * G + g[2];
-}
-
-// Validate every triangle and bound its shape (min / max on order-preserving keys).  A wave whose triangles all belong
-// to one shape reduces its box first: one set of atomics per wave, not per triangle.
-__global__ __launch_bounds__(RC_PREP_T) void rc_bound_kernel(RcMesh m, RcWs w, int32_t* __restrict__ status) {
-  const int64_t total = m.tri_off[m.batch];
-  const int64_t stride = (int64_t)gridDim.x * RC_PREP_T;
-  for (int64_t t0 = (int64_t)blockIdx.x * RC_PREP_T; t0 < total; t0 += stride) {      // uniform in a block
-    const int64_t t = t0 + threadIdx.x;
-    const int b = ms_shape_of(m.tri_off, m.batch, t < total ? t : total - 1);
-    float c[9], lo[3], hi[3];
-    const bool in = t < total;
-    const bool ok = in && ms_load(m.verts, m.faces, m.vert_off, t, b, c);
-    if (in && !ok) atomicOr(&status[b], 1);
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      lo[a] = ok ? fminf(fminf(c[a], c[3 + a]), c[6 + a]) : INFINITY;
-      hi[a] = ok ? fmaxf(fmaxf(c[a], c[3 + a]), c[6 + a]) : -INFINITY;
-    }
-    const bool one = __shfl(b, 0) == __shfl(b, MS_T - 1);        // shapes are non-decreasing along t
-    if (one) {
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        lo[a] = ms_wave_min(lo[a]);
-        hi[a] = ms_wave_max(hi[a]);
-      }
-    }
-    if (one ? ((threadIdx.x & (MS_T - 1)) == 0 && lo[0] <= hi[0]) : ok) {
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        atomicMin(&w.sbox[b * 6 + a], ms_key(lo[a]));
-        atomicMax(&w.sbox[b * 6 + 3 + a], ms_key(hi[a]));
-      }
-    }
-  }
-}
-
-// STEP 1: count and bound the bins; 2: copy the records into bin order.
-template <int STEP>
-__global__ __launch_bounds__(RC_PREP_T) void rc_bin_kernel(RcMesh m, RcWs w) {
-  const int64_t total = m.tri_off[m.batch];
-  const int64_t stride = (int64_t)gridDim.x * RC_PREP_T;
-  for (int64_t t = (int64_t)blockIdx.x * RC_PREP_T + threadIdx.x; t < total; t += stride) {
-    const int b = ms_shape_of(m.tri_off, m.batch, t);
-    float c[9];
-    if (!ms_load(m.verts, m.faces, m.vert_off, t, b, c)) continue;      // rc_bound_kernel has set the status
-    const int64_t bin = (int64_t)b * m.GS + rc_bin_of(w.sbox, b, rc_G(m, b), c);
-    if (STEP == 1) {
-      atomicAdd(&w.cnt[bin], 1);
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        atomicMin(&w.box[bin * 6 + a], ms_key(fminf(fminf(c[a], c[3 + a]), c[6 + a])));
-        atomicMax(&w.box[bin * 6 + 3 + a], ms_key(fmaxf(fmaxf(c[a], c[3 + a]), c[6 + a])));
-      }
-    } else {
-      const int64_t slot = (int64_t)w.off[bin] + atomicAdd(&w.cursor[bin], 1);
-#pragma unroll
-      for (int k = 0; k < 9; ++k) w.tri[slot * RC_W + k] = c[k];
-      w.tri[slot * RC_W + 9] = __int_as_float((int32_t)(t - m.tri_off[b]));
-    }
-  }
-}
 
 // A ray the cast answers: every component finite and a direction that is not zero.
 __device__ __forceinline__ bool rc_valid(const float (&o)[3], const float (&d)[3]) {
@@ -211,9 +48,9 @@ __device__ __forceinline__ bool rc_valid(const float (&o)[3], const float (&d)[3
 }
 
 // Sort key of every ray.  Only the shape bits matter for the result (a shape's rays stay in its range of positions).
-__global__ __launch_bounds__(RC_PREP_T) void rc_key_kernel(RcMesh m, RcWs w, int64_t total_q) {
-  const int64_t stride = (int64_t)gridDim.x * RC_PREP_T;
-  for (int64_t i = (int64_t)blockIdx.x * RC_PREP_T + threadIdx.x; i < total_q; i += stride) {
+__global__ __launch_bounds__(TB_PREP_T) void rc_key_kernel(RcMesh m, TbBins w, TbOrder ord, int64_t total_q) {
+  const int64_t stride = (int64_t)gridDim.x * TB_PREP_T;
+  for (int64_t i = (int64_t)blockIdx.x * TB_PREP_T + threadIdx.x; i < total_q; i += stride) {
     const int b = ms_shape_of(m.ray_off, m.batch, i);
     float o[3], d[3];
     int cell[3];
@@ -227,8 +64,8 @@ __global__ __launch_bounds__(RC_PREP_T) void rc_key_kernel(RcMesh m, RcWs w, int
     }
     const uint64_t oct = (d[0] < 0.f ? 4u : 0u) | (d[1] < 0.f ? 2u : 0u) | (d[2] < 0.f ? 1u : 0u);
     const uint64_t code = rc_valid(o, d) ? ((ofx_xyz2morton(cell[0], cell[1], cell[2]) << 3) | oct) : (1ull << 30);
-    w.key[i] = (int64_t)(((uint64_t)b << 32) | code);
-    w.idx[i] = (int32_t)i;
+    ord.key[i] = (int64_t)(((uint64_t)b << 32) | code);
+    ord.idx[i] = (int32_t)i;
   }
 }
 
@@ -317,7 +154,7 @@ __device__ __forceinline__ bool rc_slab(const float (&o)[3], const float (&inv)[
 }
 
 template <bool COUNT>
-__global__ __launch_bounds__(MS_T) void rc_cast_kernel(RcMesh m, RcWs ws, const int32_t* __restrict__ order,
+__global__ __launch_bounds__(MS_T) void rc_cast_kernel(RcMesh m, TbBins ws, const int32_t* __restrict__ order,
                                                        const int32_t* __restrict__ status, float tmin, float tmax,
                                                        float* __restrict__ t_out, int32_t* __restrict__ face_out,
                                                        float* __restrict__ point, float* __restrict__ cosn,
@@ -366,7 +203,7 @@ __global__ __launch_bounds__(MS_T) void rc_cast_kernel(RcMesh m, RcWs ws, const 
   const int lead = __ffsll((unsigned long long)acts) - 1;
   const int wk = __shfl(r.kz, lead);
   const bool wneg = __shfl((int)(rc_pick((double)d[0], (double)d[1], (double)d[2], r.kz) < 0.0), lead) != 0;
-  const int G = rc_G(m, b), G2 = G * G;
+  const int G = tb_G(m, b), G2 = G * G;
   const int64_t bin0 = (int64_t)b * m.GS;
   double best = INFINITY;
   int32_t bf = INT32_MAX;
@@ -408,8 +245,8 @@ __global__ __launch_bounds__(MS_T) void rc_cast_kernel(RcMesh m, RcWs ws, const 
           const int n = count - base < MS_T ? count - base : MS_T;
           if (lane < n) {
 #pragma unroll
-            for (int k = 0; k < 9; ++k) rec[k * MS_T + lane] = ws.tri[(start + base + lane) * RC_W + k];
-            ids[lane] = __float_as_int(ws.tri[(start + base + lane) * RC_W + 9]);
+            for (int k = 0; k < 9; ++k) rec[k * MS_T + lane] = ws.tri[(start + base + lane) * TB_W + k];
+            ids[lane] = __float_as_int(ws.tri[(start + base + lane) * TB_W + 9]);
           }
           __syncthreads();
           for (int j = 0; j < n; ++j) {
@@ -572,17 +409,12 @@ __global__ void rs_offsets_kernel(const int64_t* __restrict__ ray_off, int batch
 
 unsigned long long* rc_counters = nullptr;      // ofx_ray_cast_set_counters
 
-bool rc_args_ok(int batch, int64_t total_verts, int64_t total_faces, int64_t total_q, int bins) {
-  return batch >= 1 && batch <= 65535 && total_verts >= 1 && total_faces >= 1 && total_faces <= INT32_MAX &&
-         total_q >= 0 && total_q <= (int64_t(1) << 30) && bins >= 0 && bins <= RC_MAX_G;
-}
-
 inline size_t rs_layout(int64_t total_q, char* base, int32_t** blk, int32_t** blk_off, void** scan_ws) {
   const int64_t nblk = ofx_cdiv(total_q > 0 ? total_q : 1, RS_T);
   size_t o = 0;
   auto take = [&](size_t bytes) {
     char* p = base ? base + o : nullptr;
-    o += rc_align(bytes);
+    o += tb_align(bytes);
     return p;
   };
   int32_t* a = (int32_t*)take(nblk * sizeof(int32_t));
@@ -598,8 +430,8 @@ inline size_t rs_layout(int64_t total_q, char* base, int32_t** blk, int32_t** bl
 
 extern "C" size_t ofx_ray_cast_ws_bytes(int batch, int64_t total_verts, int64_t total_faces, int64_t total_q,
                                         int bins) {
-  if (!rc_args_ok(batch, total_verts, total_faces, total_q, bins)) return 0;
-  return rc_layout(batch, total_faces, total_q, bins, nullptr, nullptr);
+  if (!ofx_tribins_args_ok(batch, total_verts, total_faces, total_q, bins)) return 0;
+  return ofx_tribins_layout(batch, total_faces, total_q, bins, nullptr, nullptr, nullptr);
 }
 
 extern "C" int ofx_ray_cast_set_counters(unsigned long long* words) {
@@ -612,34 +444,23 @@ extern "C" int ofx_ray_cast(const float* verts, const int32_t* faces, const int6
                             int64_t max_q, float tmin, float tmax, int bins, int coherent, float* t, int32_t* face,
                             float* point, float* cosn, void* ws, int32_t* status, void* stream) {
   if (!verts || !faces || !vert_off || !tri_off || !ray_off || !ws || !status ||
-      !rc_args_ok(batch, 1, 1, total_q, bins) || max_q < 0 || max_q > total_q || tmin != tmin || tmax != tmax ||
+      !ofx_tribins_args_ok(batch, 1, 1, total_q, bins) || max_q < 0 || max_q > total_q || tmin != tmin || tmax != tmax ||
       (total_q > 0 && (!org || !dir || !t || !face || max_q < 1)))
     return OFX_EINVAL;
   hipStream_t st = ofx_stream(stream);
-  const int GS = rc_stride(bins);
-  const int64_t nb = (int64_t)batch * GS;
-  RcWs w;
-  rc_layout(batch, 0, total_q, bins, (char*)ws, &w);   // the face-sized array is the last one: its size is not needed
-  const RcMesh m{verts, faces, vert_off, tri_off, org, dir, ray_off, batch, bins, GS};
-  rc_init_kernel<<<ofx_grid(nb, RC_PREP_T), RC_PREP_T, 0, st>>>(nb, w, batch, status);
-  OFX_LAUNCH_CHECK();
-  const int prep = 2048;                          // grid-stride: the face count lives on the device
-  rc_bound_kernel<<<prep, RC_PREP_T, 0, st>>>(m, w, status);
-  OFX_LAUNCH_CHECK();
-  if (total_q == 0) return OFX_OK;                // the status words are still written
-  rc_bin_kernel<1><<<prep, RC_PREP_T, 0, st>>>(m, w);
-  OFX_LAUNCH_CHECK();
-  int rc = ofx_scan_i32(w.cnt, w.off, nb, w.scan_ws, stream);
-  if (rc) return rc;
-  rc_bin_kernel<2><<<prep, RC_PREP_T, 0, st>>>(m, w);
-  OFX_LAUNCH_CHECK();
+  TbBins w;
+  TbOrder o;
+  ofx_tribins_layout(batch, 0, total_q, bins, (char*)ws, &w, &o);   // the records are last: their size is not needed
+  const RcMesh m{{verts, faces, vert_off, tri_off, batch, bins, tb_stride(bins)}, org, dir, ray_off};
+  int rc = ofx_tribins_build(m, w, total_q, status, stream);
+  if (rc || total_q == 0) return rc;              // no rays: the status words are still written
   const int32_t* order = nullptr;
   if (!coherent) {
-    rc_key_kernel<<<ofx_grid(total_q, RC_PREP_T), RC_PREP_T, 0, st>>>(m, w, total_q);
+    rc_key_kernel<<<ofx_grid(total_q, TB_PREP_T), TB_PREP_T, 0, st>>>(m, w, o, total_q);
     OFX_LAUNCH_CHECK();
-    rc = ofx_points_sort(w.key, w.idx, total_q, w.skey, w.sidx, w.sort_ws, w.sort_bytes, stream);
+    rc = ofx_points_sort(o.key, o.idx, total_q, o.skey, o.sidx, o.sort_ws, o.sort_bytes, stream);
     if (rc) return rc;
-    order = w.sidx;
+    order = o.sidx;
   }
   const dim3 waves((unsigned)ofx_cdiv(max_q, MS_T), (unsigned)batch);
   if (rc_counters)
@@ -668,7 +489,7 @@ extern "C" int ofx_ray_scan(const float* verts, const int32_t* faces, const int6
   void* scan_ws;
   rs_layout(total_q, (char*)ws, &blk, &blk_off, &scan_ws);
   const int64_t nblk = ofx_cdiv(total_q > 0 ? total_q : 1, RS_T);
-  const RcMesh m{verts, faces, vert_off, tri_off, org, dir, ray_off, batch, 0, 0};
+  const RcMesh m{{verts, faces, vert_off, tri_off, batch, 0, 0}, org, dir, ray_off};
   rs_count_kernel<<<(unsigned)nblk, RS_T, 0, st>>>(face, total_q, blk);
   OFX_LAUNCH_CHECK();
   const int rc = ofx_scan_i32(blk, blk_off, nblk, scan_ws, stream);

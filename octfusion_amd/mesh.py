@@ -308,6 +308,81 @@ def _cat(meshes):
     return torch.cat([v for v, _ in meshes]).contiguous(), torch.cat([f for _, f in meshes]).contiguous()
 
 
+# ---- the triangle bins (csrc/ofx_tribins.hip): what the callers of ofx_mesh_query and ofx_ray_cast share -----------
+MAX_BINS = 16
+_MAX_Q = 2 ** 30
+
+
+def _gather(meshes, sets, bins, who, noun):
+    """The argument checks and the concatenated arrays of one call that searches the bins of ``meshes``.
+
+    sets: ``(what, label, value)`` per kind of per-mesh ``[n, 3]`` fp32 set -- ``what`` names one set and keys the
+    result, ``label`` names the list (``('points', 'point sets', points)``); value is a list of B tensors or one
+    ``[B, n, 3]`` tensor.  Every kind has the same count per mesh.  who, noun: the caller and what it counts
+    (``'queries'``), for the messages.  Returns a dict: verts, faces, one concatenated tensor per ``what``, offs
+    ``[3, B + 1]`` int64 on the device (vertices, faces, items), the host lists nv, nf, nq, and B, bins, dev."""
+    bins = int(bins)
+    if not 0 <= bins <= MAX_BINS:
+        raise ValueError('%s: bins %d outside [0, %d]' % (who, bins, MAX_BINS))
+    meshes = _check_meshes(meshes, who)
+    if not meshes:
+        raise ValueError('%s: no meshes' % who)
+    B, dev = len(meshes), meshes[0][0].device
+    for k, (v, f) in enumerate(meshes):
+        if f.shape[0] == 0 or v.shape[0] == 0:
+            raise ValueError('%s: shape %d has no faces' % (who, k))
+        if v.device != dev:
+            raise ValueError('%s: shape %d is on another device' % (who, k))
+    lists = []
+    for what, label, value in sets:
+        if torch.is_tensor(value) and (value.dim() != 3 or value.shape[2] != 3):
+            raise ValueError('%s: a stacked batch of %s must be [B, n, 3], got %s' % (who, what, tuple(value.shape)))
+        value = list(value)
+        if len(value) != B:
+            raise ValueError('%s: %d %s for %d meshes' % (who, len(value), label, B))
+        for k, p in enumerate(value):
+            if not torch.is_tensor(p) or p.dim() != 2 or p.shape[1] != 3:
+                raise ValueError('%s: %s %d must be a [n, 3] tensor' % (who, what, k))
+            if p.dtype != torch.float32:
+                raise ValueError('%s: %s %d must be float32, got %s' % (who, what, k, p.dtype))
+            if p.device != dev:
+                raise ValueError('%s: %s %d are not on the device of the meshes' % (who, what, k))
+            if lists and p.shape[0] != lists[0][k].shape[0]:
+                raise ValueError('%s: %d %s for %d %s of shape %d'
+                                 % (who, lists[0][k].shape[0], sets[0][0], p.shape[0], what, k))
+        lists.append(value)
+    nv = [int(v.shape[0]) for v, _ in meshes]
+    nf = [int(f.shape[0]) for _, f in meshes]
+    nq = [int(p.shape[0]) for p in lists[0]]
+    if sum(nf) > _INT32_MAX or sum(nq) > _MAX_Q or B > 65535:
+        raise ValueError('%s: %d shapes, %d faces, %d %s exceed one call (65535, 2^31 - 1, 2^30)'
+                         % (who, B, sum(nf), sum(nq), noun))
+    verts, faces = _cat(meshes)
+    offs = torch.from_numpy(np.stack([np.cumsum([0] + nv), np.cumsum([0] + nf),
+                                      np.cumsum([0] + nq)]).astype(np.int64)).to(dev)
+    g = dict(verts=verts, faces=faces, offs=offs, nv=nv, nf=nf, nq=nq, B=B, bins=bins, dev=dev)
+    for (what, _, _), value in zip(sets, lists):
+        g[what] = value[0].contiguous() if B == 1 else torch.cat(value).contiguous()
+    return g
+
+
+def _bins_ws(g, ws_bytes, who, noun):
+    """The workspace of a gathered call, sized by the library's ``ws_bytes`` entry (its name)."""
+    sizes = (g['B'], sum(g['nv']), sum(g['nf']), sum(g['nq']))
+    nbytes = getattr(_lib.lib(), ws_bytes)(*sizes, g['bins'])
+    if nbytes == 0:
+        raise ValueError('%s: %d shapes, %d vertices, %d faces, %d %s out of range' % ((who,) + sizes + (noun,)))
+    return torch.empty(nbytes, dtype=torch.uint8, device=g['dev'])
+
+
+def _raise_bad_shape(status, g, who):
+    """Reads the status words of a gathered call (a host read) and refuses the first shape the device refused."""
+    bad = torch.nonzero(status).flatten().tolist()
+    if bad:
+        raise ValueError('%s: shape %d has a face index outside [0, %d) or a non-finite vertex'
+                         % (who, bad[0], g['nv'][bad[0]]))
+
+
 def _label(verts, faces, nv, nf):
     """Label one batch mesh: (offsets [2, B + 1] on the device, label, workspace, status words)."""
     B, V, F = len(nv), sum(nv), sum(nf)

@@ -20,26 +20,7 @@ import torch
 from . import _lib, mesh, metrics
 from ._lib import call, ptr, stream
 
-MAX_BINS = 16
-_INT32_MAX = 2 ** 31 - 1
-_MAX_Q = 2 ** 30
-
-
-def _points_list(points, n_meshes, dev):
-    stacked = torch.is_tensor(points)
-    if stacked and (points.dim() != 3 or points.shape[2] != 3):
-        raise ValueError('closest_point: a stacked batch of points must be [B, n, 3], got %s' % (tuple(points.shape),))
-    pts = list(points)
-    if len(pts) != n_meshes:
-        raise ValueError('closest_point: %d point sets for %d meshes' % (len(pts), n_meshes))
-    for k, p in enumerate(pts):
-        if not torch.is_tensor(p) or p.dim() != 2 or p.shape[1] != 3:
-            raise ValueError('closest_point: points %d must be a [n, 3] tensor' % k)
-        if p.dtype != torch.float32:
-            raise ValueError('closest_point: points %d must be float32, got %s' % (k, p.dtype))
-        if p.device != dev:
-            raise ValueError('closest_point: points %d are not on the device of the meshes' % k)
-    return pts
+MAX_BINS = mesh.MAX_BINS
 
 
 def closest_point(meshes, points, signed=False, bins=0, want_point=True):
@@ -63,47 +44,21 @@ def closest_point(meshes, points, signed=False, bins=0, want_point=True):
     Raises ValueError naming the mesh for a mesh without faces, a face index outside ``[0, V)`` or a non-finite vertex
     used by a face; ValueError for wrong dtypes, shapes or ``bins`` before anything is launched."""
     _lib.require_device()
-    bins = int(bins)
-    if not 0 <= bins <= MAX_BINS:
-        raise ValueError('closest_point: bins %d outside [0, %d]' % (bins, MAX_BINS))
-    meshes = mesh._check_meshes(meshes, 'closest_point')
-    if not meshes:
-        raise ValueError('closest_point: no meshes')
-    dev = meshes[0][0].device
-    for k, (v, f) in enumerate(meshes):
-        if f.shape[0] == 0 or v.shape[0] == 0:
-            raise ValueError('closest_point: shape %d has no faces' % k)
-        if v.device != dev:
-            raise ValueError('closest_point: shape %d is on another device' % k)
-    pts = _points_list(points, len(meshes), dev)
-    B = len(meshes)
-    nv = [int(v.shape[0]) for v, _ in meshes]
-    nf = [int(f.shape[0]) for _, f in meshes]
-    nq = [int(p.shape[0]) for p in pts]
+    who = 'closest_point'
+    g = mesh._gather(meshes, [('points', 'point sets', points)], bins, who, 'queries')
+    B, nq, dev = g['B'], g['nq'], g['dev']
     Q = sum(nq)
-    if sum(nf) > _INT32_MAX or Q > _MAX_Q or B > 65535:
-        raise ValueError('closest_point: %d shapes, %d faces, %d queries exceed one call (65535, 2^31 - 1, 2^30)'
-                         % (B, sum(nf), Q))
-    verts, faces = mesh._cat(meshes)
-    q = pts[0].contiguous() if B == 1 else torch.cat(pts).contiguous()
-    offs = torch.from_numpy(np.stack([np.cumsum([0] + nv), np.cumsum([0] + nf),
-                                      np.cumsum([0] + nq)]).astype(np.int64)).to(dev)
-    nbytes = _lib.lib().ofx_mesh_query_ws_bytes(B, sum(nv), sum(nf), Q, bins)
-    if nbytes == 0:
-        raise ValueError('closest_point: %d shapes, %d vertices, %d faces, %d queries out of range'
-                         % (B, sum(nv), sum(nf), Q))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = mesh._bins_ws(g, 'ofx_mesh_query_ws_bytes', who, 'queries')
     dist = torch.empty(Q, dtype=torch.float32, device=dev)
     face = torch.empty(Q, dtype=torch.int32, device=dev)
     point = torch.empty(Q, 3, dtype=torch.float32, device=dev) if want_point else None
     status = torch.empty(B, dtype=torch.int32, device=dev)
-    call('ofx_mesh_query', ptr(verts), ptr(faces), ptr(offs[0]), ptr(offs[1]), ptr(q) if Q else None, ptr(offs[2]), B,
-         Q, max(nq), bins, 1 if signed else 0, ptr(dist) if Q else None, ptr(face) if Q else None,
-         ptr(point) if want_point and Q else None, ptr(ws), ptr(status), stream())
-    bad = torch.nonzero(status).flatten().tolist()              # the host read
-    if bad:
-        raise ValueError('closest_point: shape %d has a face index outside [0, %d) or a non-finite vertex'
-                         % (bad[0], nv[bad[0]]))
+    offs = g['offs']
+    call('ofx_mesh_query', ptr(g['verts']), ptr(g['faces']), ptr(offs[0]), ptr(offs[1]),
+         ptr(g['points']) if Q else None, ptr(offs[2]), B, Q, max(nq), g['bins'], 1 if signed else 0,
+         ptr(dist) if Q else None, ptr(face) if Q else None, ptr(point) if want_point and Q else None, ptr(ws),
+         ptr(status), stream())
+    mesh._raise_bad_shape(status, g, who)                       # the host read
     ds, fs = dist.split(nq), face.split(nq)
     ps = point.split(nq) if want_point else [None] * B
     return [(ds[k], fs[k], ps[k]) for k in range(B)]

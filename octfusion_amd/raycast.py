@@ -24,61 +24,14 @@ import torch
 from . import _lib, mesh, render
 from ._lib import call, ptr, stream
 
-MAX_BINS = 16
+MAX_BINS = mesh.MAX_BINS
 TILE = 8
-_INT32_MAX = 2 ** 31 - 1
-_MAX_Q = 2 ** 30
-
-
-def _ray_list(rays, what, n_meshes, dev):
-    stacked = torch.is_tensor(rays)
-    if stacked and (rays.dim() != 3 or rays.shape[2] != 3):
-        raise ValueError('ray_cast: a stacked batch of %s must be [B, n, 3], got %s' % (what, tuple(rays.shape)))
-    sets = list(rays)
-    if len(sets) != n_meshes:
-        raise ValueError('ray_cast: %d sets of %s for %d meshes' % (len(sets), what, n_meshes))
-    for k, p in enumerate(sets):
-        if not torch.is_tensor(p) or p.dim() != 2 or p.shape[1] != 3:
-            raise ValueError('ray_cast: %s %d must be a [n, 3] tensor' % (what, k))
-        if p.dtype != torch.float32:
-            raise ValueError('ray_cast: %s %d must be float32, got %s' % (what, k, p.dtype))
-        if p.device != dev:
-            raise ValueError('ray_cast: %s %d are not on the device of the meshes' % (what, k))
-    return sets
 
 
 def _gather(meshes, origins, dirs, bins, who='ray_cast'):
-    """The argument checks of ``closest_point`` and the concatenated arrays of one call."""
-    bins = int(bins)
-    if not 0 <= bins <= MAX_BINS:
-        raise ValueError('%s: bins %d outside [0, %d]' % (who, bins, MAX_BINS))
-    meshes = mesh._check_meshes(meshes, who)
-    if not meshes:
-        raise ValueError('%s: no meshes' % who)
-    dev = meshes[0][0].device
-    for k, (v, f) in enumerate(meshes):
-        if f.shape[0] == 0 or v.shape[0] == 0:
-            raise ValueError('%s: shape %d has no faces' % (who, k))
-        if v.device != dev:
-            raise ValueError('%s: shape %d is on another device' % (who, k))
-    org = _ray_list(origins, 'origins', len(meshes), dev)
-    dr = _ray_list(dirs, 'directions', len(meshes), dev)
-    for k, (o, d) in enumerate(zip(org, dr)):
-        if o.shape[0] != d.shape[0]:
-            raise ValueError('ray_cast: %d origins for %d directions of shape %d' % (o.shape[0], d.shape[0], k))
-    B = len(meshes)
-    nv = [int(v.shape[0]) for v, _ in meshes]
-    nf = [int(f.shape[0]) for _, f in meshes]
-    nq = [int(o.shape[0]) for o in org]
-    if sum(nf) > _INT32_MAX or sum(nq) > _MAX_Q or B > 65535:
-        raise ValueError('%s: %d shapes, %d faces, %d rays exceed one call (65535, 2^31 - 1, 2^30)'
-                         % (who, B, sum(nf), sum(nq)))
-    verts, faces = mesh._cat(meshes)
-    o = org[0].contiguous() if B == 1 else torch.cat(org).contiguous()
-    d = dr[0].contiguous() if B == 1 else torch.cat(dr).contiguous()
-    offs = torch.from_numpy(np.stack([np.cumsum([0] + nv), np.cumsum([0] + nf),
-                                      np.cumsum([0] + nq)]).astype(np.int64)).to(dev)
-    return dict(verts=verts, faces=faces, org=o, dir=d, offs=offs, nv=nv, nf=nf, nq=nq, B=B, bins=bins, dev=dev)
+    """``mesh._gather`` for rays: the concatenated rays are its ``'origins'`` and ``'directions'``."""
+    return mesh._gather(meshes, [('origins', 'sets of origins', origins), ('directions', 'sets of directions', dirs)],
+                        bins, who, 'rays')
 
 
 def _cast(g, tmin, tmax, want_point, want_cos, coherent, who='ray_cast'):
@@ -87,25 +40,19 @@ def _cast(g, tmin, tmax, want_point, want_cos, coherent, who='ray_cast'):
     if math.isnan(tmin) or math.isnan(tmax):
         raise ValueError('%s: tmin and tmax must not be NaN' % who)
     B, Q, dev = g['B'], sum(g['nq']), g['dev']
-    nbytes = _lib.lib().ofx_ray_cast_ws_bytes(B, sum(g['nv']), sum(g['nf']), Q, g['bins'])
-    if nbytes == 0:
-        raise ValueError('%s: %d shapes, %d vertices, %d faces, %d rays out of range'
-                         % (who, B, sum(g['nv']), sum(g['nf']), Q))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = mesh._bins_ws(g, 'ofx_ray_cast_ws_bytes', who, 'rays')
     t = torch.empty(Q, dtype=torch.float32, device=dev)
     face = torch.empty(Q, dtype=torch.int32, device=dev)
     point = torch.empty(Q, 3, dtype=torch.float32, device=dev) if want_point else None
     cosn = torch.empty(Q, dtype=torch.float32, device=dev) if want_cos else None
     status = torch.empty(B, dtype=torch.int32, device=dev)
     offs = g['offs']
-    call('ofx_ray_cast', ptr(g['verts']), ptr(g['faces']), ptr(offs[0]), ptr(offs[1]), ptr(g['org']) if Q else None,
-         ptr(g['dir']) if Q else None, ptr(offs[2]), B, Q, max(g['nq']), tmin, tmax, g['bins'], 1 if coherent else 0,
-         ptr(t) if Q else None, ptr(face) if Q else None, ptr(point) if want_point and Q else None,
-         ptr(cosn) if want_cos and Q else None, ptr(ws), ptr(status), stream())
-    bad = torch.nonzero(status).flatten().tolist()              # the host read
-    if bad:
-        raise ValueError('%s: shape %d has a face index outside [0, %d) or a non-finite vertex'
-                         % (who, bad[0], g['nv'][bad[0]]))
+    call('ofx_ray_cast', ptr(g['verts']), ptr(g['faces']), ptr(offs[0]), ptr(offs[1]),
+         ptr(g['origins']) if Q else None, ptr(g['directions']) if Q else None, ptr(offs[2]), B, Q, max(g['nq']), tmin,
+         tmax, g['bins'], 1 if coherent else 0, ptr(t) if Q else None, ptr(face) if Q else None,
+         ptr(point) if want_point and Q else None, ptr(cosn) if want_cos and Q else None, ptr(ws), ptr(status),
+         stream())
+    mesh._raise_bad_shape(status, g, who)                       # the host read
     return t, face, point, cosn
 
 
@@ -278,7 +225,7 @@ def virtual_scan(meshes, poses, size=128, noise=0.0, seed=0, bins=0):
     def rows(x):                    # tile order -> row-major pixels within each view: the order of the compacted cloud
         x = x.view(B, V, S * S, *x.shape[1:])
         return x[:, :, inv].reshape(B * V * S * S, *x.shape[3:]).contiguous()
-    t, face, org, dr = rows(t), rows(face), rows(g['org']), rows(g['dir'])
+    t, face, org, dr = rows(t), rows(face), rows(g['origins']), rows(g['directions'])
     Q = sum(g['nq'])
     ws = torch.empty(max(1, _lib.lib().ofx_ray_scan_ws_bytes(Q)), dtype=torch.uint8, device=dev)
     points = torch.empty(Q, 3, dtype=torch.float32, device=dev)

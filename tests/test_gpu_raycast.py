@@ -374,6 +374,19 @@ def test_wrong_arguments_raise_before_a_launch(scenes):
         assert rc == -1 and status.tolist() == [77] and (t[0] == 77).all() and (face[0] == 77).all()
 
 
+def test_workspace_sizes_are_those_of_the_separate_builders():
+    """ofx_mesh_query and ofx_ray_cast carve one layout (ofx_tribins_layout).  The literals are what each entry returned
+    for (batch, verts, faces, items, bins) on an MI355X while it still had a layout of its own (the sort's share, which
+    weighs in the last one, is the device's answer): a caller's workspace stays valid."""
+    from octfusion_amd import _lib
+    L = _lib.lib()
+    for args, nbytes in (((1, 8, 12, 10, 0), 150272), ((1, 8, 12, 10, 4), 5120), ((3, 100, 1000, 0, 1), 41984),
+                         ((2, 50000, 100000, 1000000, 16), 40303616)):
+        assert L.ofx_mesh_query_ws_bytes(*args) == nbytes, args
+        assert L.ofx_ray_cast_ws_bytes(*args) == nbytes, args
+        assert L.ofx_mesh_query_ws_bytes(*args) == L.ofx_ray_cast_ws_bytes(*args)
+
+
 # ---- 7 culling ----------------------------------------------------------------------------------------------------
 def test_culling_happens(scenes, results):
     from octfusion_amd import _lib
