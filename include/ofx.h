@@ -1150,6 +1150,42 @@ int ofx_mesh_query(const float* verts, const int32_t* faces, const int64_t* vert
  * evaluated after the per-triangle box test (x 64 = point-triangle pairs).  NULL: counting off.  Sticky. */
 int ofx_mesh_query_set_counters(unsigned long long* words);
 
+/* ------------------------------------------------------------------ winding numbers (csrc/ofx_winding.hip)
+ * The generalized winding number of arbitrary points around triangle meshes (Jacobson et al. 2013): the robust inside /
+ * outside of meshes that are open, self-intersecting or nested, where ray parity means nothing.  The sibling of
+ * ofx_mesh_query: meshes, queries, q_off, max_q, status, bins and every argument range are exactly its own.
+ * tests/winding_oracle.py restates the contract in float64.
+ *   The pair (query p, triangle), in fp64 with every operation rounded on its own: a, b, c = the vertices minus p;
+ *     num = a . (b x c); den = ((|a| |b|) |c| + (a . b) |c|) + (b . c) |a|) + (c . a) |b|, dots as (x x + y y) + z z;
+ *     the term is atan2(num, den) (van Oosterom and Strackee), and a sum S of terms counts as (2 S) / (4 pi) turns.
+ *     A triangle whose fp64 (b - a) x (c - a) is exactly zero contributes nothing, in either mode.
+ *   w [Q] fp32: the sum below, rounded once.  A query with a non-finite coordinate gets NaN and changes no other
+ *     query's result; a shape with a non-zero status has its outputs left unwritten.
+ *   beta == 0, exact: S = the terms of ALL the shape's triangles added in face-index order, starting from 0;
+ *     w = (2 S) / (4 pi).  A pure function of (mesh, query), bitwise: the same alone or in a batch, for any order of
+ *     the queries and for any bins -- the bins are not read and not built in this mode.
+ *   beta > 0, far field (first order, after Barill et al. 2018): per non-empty bin k of the G^3 grid of ofx_mesh_query,
+ *     over its triangles with a non-zero (b - a) x (c - a), in face-index order 64 at a time (the 64 values added in
+ *     a fixed tree, the chunks in turn): N_k = sum of (b - a) x (c - a) / 2; centre_k = sum of area x centroid / sum of
+ *     area, area = |(b - a) x (c - a)| / 2, centroid = ((a + b) + c) / 3; r_k = the largest distance from centre_k to
+ *     a vertex of those triangles.  With d = centre_k - p, the bin is far for p iff |d| > beta r_k and then contributes
+ *     (N_k . d) / (4 pi |d|^3); otherwise it contributes (2 S_k) / (4 pi), S_k = the terms of its triangles added in
+ *     face-index order from 0.  w = the contributions added in bin-index order from 0.  The result depends on bins and
+ *     beta, as the approximation does; it is bitwise the same from run to run, for any order of the queries and in any
+ *     batch.  Putting a bin's faces in order costs the square of its size: choose bins so that bins stay small (the
+ *     automatic rule does).
+ *   beta: finite and >= 0.  ws: ofx_mesh_winding_ws_bytes (0 for arguments out of range, the ranges of
+ *   ofx_mesh_query_ws_bytes).  Bad arguments: OFX_EINVAL, nothing launched.  No floating-point atomics. */
+size_t ofx_mesh_winding_ws_bytes(int batch, int64_t total_verts, int64_t total_faces, int64_t total_q, int bins);
+int ofx_mesh_winding(const float* verts, const int32_t* faces, const int64_t* vert_off, const int64_t* tri_off,
+                     const float* q, const int64_t* q_off, int batch, int64_t total_q, int64_t max_q, int bins,
+                     float beta, float* w, void* ws, int32_t* status, void* stream);
+/* Measurement aid (tools/winding_probe.py; not on the operator path), as ofx_mesh_query_set_counters but >= 4 zeroed
+ * words: per wave of 64 queries words[0] += bins that were far for every query of the wave (never staged),
+ * words[1] += triangles staged, words[2] += (query, triangle) pairs that entered a sum, words[3] += dipoles taken.
+ * NULL: counting off.  Sticky. */
+int ofx_mesh_winding_set_counters(unsigned long long* words);
+
 /* ------------------------------------------------------------------ ray -> mesh casts (csrc/ofx_raycast.hip)
  * The first hit of arbitrary rays on triangle meshes, exact and bit-reproducible: the sibling of ofx_mesh_query.
  * tests/raycast_oracle.py restates the contract in float64.  Meshes concatenated as for ofx_mesh_query (verts, faces,

@@ -5,8 +5,8 @@
 //   bins   the per-shape G^3 centroid bins of ofx_tribins.h, built by ofx_tribins_build: the structure the ray casts
 //          search too.  G is given or comes from the shape's face count (tb_bins).  Nothing below depends on which
 //          bin a triangle is in or on the order inside a bin.
-//   order  a key per query: shape << 32 | non-finite << 30 | 30-bit Morton code of the query clamped into the shape's
-//          box; ofx_points_sort orders them, so a wave gets 64 neighbouring queries.  Where the Morton order jumps
+//   order  ofx_tribins_order_points: a key per query, shape << 32 | non-finite << 30 | 30-bit Morton code of the query
+//          clamped into the shape's box, sorted, so a wave gets 64 neighbouring queries.  Where the Morton order jumps
 //          across the shape inside a wave, the wave is searched as two parts (mq_split).  Performance devices only.
 //   dist   one wave per 64 consecutive sorted queries of one shape.  K = the exact fp32 box of the wave's (or the
 //          part's) finite queries.  From there the lattice entry's search with K in place of the brick box
@@ -33,29 +33,6 @@ struct MqMesh : TbMesh {
   const float* q;
   const int64_t* q_off;
 };
-
-// Sort key of every query: shape << 32 | non-finite << 30 | Morton code of the query in a 1024^3 grid over the shape's
-// box.  Only the shape bits matter for the result (a shape's queries stay in its range of sorted positions).
-__global__ __launch_bounds__(TB_PREP_T) void mq_key_kernel(MqMesh m, TbBins w, TbOrder o, int64_t total_q) {
-  const int64_t stride = (int64_t)gridDim.x * TB_PREP_T;
-  for (int64_t i = (int64_t)blockIdx.x * TB_PREP_T + threadIdx.x; i < total_q; i += stride) {
-    const int b = ms_shape_of(m.q_off, m.batch, i);
-    uint64_t code = 0;
-    bool fin = true;
-    int cell[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      const float v = m.q[i * 3 + a];
-      fin = fin && isfinite(v);
-      const float lo = ms_unkey(w.sbox[b * 6 + a]), ext = ms_unkey(w.sbox[b * 6 + 3 + a]) - lo;
-      const float f = (v - lo) / ext * 1024.f;
-      cell[a] = f >= 0.f ? (f < 1023.f ? (int)f : 1023) : 0;      // a NaN lands in cell 0
-    }
-    code = fin ? ofx_xyz2morton(cell[0], cell[1], cell[2]) : (1ull << 30);
-    o.key[i] = (int64_t)(((uint64_t)b << 32) | code);
-    o.idx[i] = (int32_t)i;
-  }
-}
 
 // The wave's queries: lane's sorted slot -> query index qi (-1: no query), its point qf and whether it is finite.
 __device__ __forceinline__ void mq_wave(const MqMesh& m, const int32_t* __restrict__ sidx, int b, int lane, int64_t& qi,
@@ -342,9 +319,7 @@ extern "C" int ofx_mesh_query(const float* verts, const int32_t* faces, const in
   const MqMesh m{{verts, faces, vert_off, tri_off, batch, bins, tb_stride(bins)}, q, q_off};
   int rc = ofx_tribins_build(m, w, total_q, status, stream);
   if (rc || total_q == 0) return rc;              // no queries: the status words are still written
-  mq_key_kernel<<<ofx_grid(total_q, TB_PREP_T), TB_PREP_T, 0, st>>>(m, w, o, total_q);
-  OFX_LAUNCH_CHECK();
-  rc = ofx_points_sort(o.key, o.idx, total_q, o.skey, o.sidx, o.sort_ws, o.sort_bytes, stream);
+  rc = ofx_tribins_order_points(m, q, q_off, w, o, total_q, stream);
   if (rc) return rc;
   const dim3 waves((unsigned)ofx_cdiv(max_q, MS_T), (unsigned)batch);
   if (mq_counters) mq_dist_kernel<true><<<waves, MS_T, 0, st>>>(m, w, o, status, dist, face, point, mq_counters);

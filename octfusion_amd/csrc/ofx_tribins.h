@@ -67,3 +67,10 @@ size_t ofx_tribins_layout(int batch, int64_t total_faces, int64_t total_q, int b
 // Zeroes the status words, validates every triangle (status[b] |= 1 for a shape with a bad one) and bounds the shapes;
 // then, unless total_q == 0, count -> ofx_scan_i32 -> fill.  OFX_OK or the error of the step that failed.
 int ofx_tribins_build(const TbMesh& m, const TbBins& w, int64_t total_q, int32_t* status, void* stream);
+
+// Puts the Q points q [Q, 3] (q_off [batch + 1]: where each shape's begin) into o.sidx so that a wave of 64 consecutive
+// slots holds neighbours: key = shape << 32 | non-finite << 30 | 30-bit Morton code of the point clamped into the
+// shape's box (of ofx_tribins_build, which must have run), sorted by ofx_points_sort.  A shape's points stay in its own
+// range of slots; the order inside it is a performance device only.
+int ofx_tribins_order_points(const TbMesh& m, const float* q, const int64_t* q_off, const TbBins& w, const TbOrder& o,
+                             int64_t total_q, void* stream);

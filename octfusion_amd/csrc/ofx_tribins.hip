@@ -109,6 +109,31 @@ __global__ __launch_bounds__(TB_PREP_T) void tb_bin_kernel(TbMesh m, TbBins w) {
   }
 }
 
+// Sort key of every point: shape << 32 | non-finite << 30 | Morton code of the point in a 1024^3 grid over the shape's
+// box.  Only the shape bits matter for a result (a shape's points stay in its range of sorted positions).
+__global__ __launch_bounds__(TB_PREP_T) void tb_key_kernel(int batch, const float* __restrict__ q,
+                                                           const int64_t* __restrict__ q_off, TbBins w, TbOrder o,
+                                                           int64_t total_q) {
+  const int64_t stride = (int64_t)gridDim.x * TB_PREP_T;
+  for (int64_t i = (int64_t)blockIdx.x * TB_PREP_T + threadIdx.x; i < total_q; i += stride) {
+    const int b = ms_shape_of(q_off, batch, i);
+    uint64_t code = 0;
+    bool fin = true;
+    int cell[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      const float v = q[i * 3 + a];
+      fin = fin && isfinite(v);
+      const float lo = ms_unkey(w.sbox[b * 6 + a]), ext = ms_unkey(w.sbox[b * 6 + 3 + a]) - lo;
+      const float f = (v - lo) / ext * 1024.f;
+      cell[a] = f >= 0.f ? (f < 1023.f ? (int)f : 1023) : 0;      // a NaN lands in cell 0
+    }
+    code = fin ? ofx_xyz2morton(cell[0], cell[1], cell[2]) : (1ull << 30);
+    o.key[i] = (int64_t)(((uint64_t)b << 32) | code);
+    o.idx[i] = (int32_t)i;
+  }
+}
+
 }  // namespace
 
 bool ofx_tribins_args_ok(int batch, int64_t total_verts, int64_t total_faces, int64_t total_q, int bins) {
@@ -161,4 +186,11 @@ int ofx_tribins_build(const TbMesh& m, const TbBins& w, int64_t total_q, int32_t
   tb_bin_kernel<2><<<prep, TB_PREP_T, 0, st>>>(m, w);
   OFX_LAUNCH_CHECK();
   return OFX_OK;
+}
+
+int ofx_tribins_order_points(const TbMesh& m, const float* q, const int64_t* q_off, const TbBins& w, const TbOrder& o,
+                             int64_t total_q, void* stream) {
+  tb_key_kernel<<<ofx_grid(total_q, TB_PREP_T), TB_PREP_T, 0, ofx_stream(stream)>>>(m.batch, q, q_off, w, o, total_q);
+  OFX_LAUNCH_CHECK();
+  return ofx_points_sort(o.key, o.idx, total_q, o.skey, o.sidx, o.sort_ws, o.sort_bytes, stream);
 }

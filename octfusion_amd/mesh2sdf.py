@@ -17,7 +17,7 @@ restates them in float64.  Where this can differ from mesh2sdf:
     walks its own connectivity.
 
     python -m octfusion_amd.mesh2sdf --input model.obj ... --out data [--size 128] [--level 0.015] [--pointcloud]
-        [--no-fix] [--seed 0]
+        [--no-fix] [--sign winding [--beta B]] [--seed 0]
 """
 import argparse
 import os
@@ -25,7 +25,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib, mesh, metrics
+from . import _lib, mesh, mesh_query, metrics
 from ._lib import call, ptr, stream
 
 MESH_SCALE = 0.8           # tools/repair_mesh.py:127: the raw mesh is scaled into [-0.8, 0.8]^3
@@ -41,13 +41,17 @@ def _max_batch(size):
     return max(1, _INT32_MAX // size ** 3)          # keeps the lattice of one call below 2^31 values
 
 
-def mesh_to_sdf(meshes, size=128, signed=True):
+def mesh_to_sdf(meshes, size=128, signed=True, beta=0.0):
     """SDF lattices [B, S, S, S] (fp32 on the device, x slowest) of ``meshes``, a list of B
     ``(verts [V, 3] fp32, faces [F, 3] int32)`` device tensors as ``mesh.marching_cubes`` returns them.  Lattice point
     ``(i, j, k)`` sits at ``2 (i, j, k) / S - 1`` -- what ``marching_cubes(sdf, level, bbmin=-1, bbmax=1)`` and
     ``dataset.py`` assume.  The magnitude is the exact distance to the nearest triangle (zero-area triangles count as
     the segment or point they are; vertices may lie outside the cube); with ``signed`` the value is negative where
     the ray towards -x crosses the surface an odd number of times, otherwise the distance is returned unsigned.
+    ``signed='winding'``: the unsigned lattice, bit for bit, negated where the generalized winding number at the
+    lattice point (``mesh_query.winding_number`` at its fp32 rounding, ``beta`` as there; exact by default) exceeds
+    0.5 -- the sign for raw meshes that are open, self-intersecting or nested.  The lattice points are made on the
+    device; further launches and host reads of status words only.
     Bitwise reproducible, and a shape's lattice does not depend on the batch it is in.
 
     One launch group (per ``(2^31 - 1) // S^3`` shapes) and one host read, the status words.  Raises ValueError naming
@@ -63,11 +67,38 @@ def mesh_to_sdf(meshes, size=128, signed=True):
     for k, (v, f) in enumerate(meshes):
         if f.shape[0] == 0 or v.shape[0] == 0:
             raise ValueError('mesh_to_sdf: shape %d has no faces' % k)
+    by_winding = mesh_query._winding_rule(signed, 'mesh_to_sdf')
     out = []
     g = _max_batch(size)
     for b0 in range(0, len(meshes), g):
-        out.append(_group(meshes[b0:b0 + g], b0, size, signed))
-    return out[0] if len(out) == 1 else torch.cat(out)
+        out.append(_group(meshes[b0:b0 + g], b0, size, signed and not by_winding))
+    sdf = out[0] if len(out) == 1 else torch.cat(out)
+    return _sign_by_winding(meshes, sdf, size, beta) if by_winding else sdf
+
+
+_WINDING_POINTS = 1 << 24          # lattice points of one winding call (192 MiB of queries)
+
+
+def _sign_by_winding(meshes, sdf, S, beta):
+    """Negates the unsigned lattices ``sdf [B, S, S, S]`` where the winding number at the lattice point exceeds 0.5.
+    The points are made on the device, x-slabs of at most 2^24 points at a time for as many meshes as fit in that;
+    per call one host read, the status words."""
+    dev = sdf.device
+    ax = ((2.0 * torch.arange(S, dtype=torch.float64, device=dev)) / S - 1.0).float()
+    rows = max(1, _WINDING_POINTS // (S * S))                   # x-slabs per call
+    flat = sdf.view(len(meshes), -1)
+    for i0 in range(0, S, rows):
+        i1 = min(S, i0 + rows)
+        pts = torch.stack(torch.meshgrid(ax[i0:i1], ax, ax, indexing='ij'), dim=-1).reshape(-1, 3).contiguous()
+        n = int(pts.shape[0])
+        per = max(1, _WINDING_POINTS // n)
+        for b0 in range(0, len(meshes), per):
+            part = meshes[b0:b0 + per]
+            inside = mesh_query.occupancy(part, [pts] * len(part), beta=beta)
+            for k, occ in enumerate(inside):
+                seg = flat[b0 + k, i0 * S * S:i1 * S * S]
+                seg.copy_(torch.where(occ, -seg, seg))
+    return sdf
 
 
 def _group(part, b0, S, signed):
@@ -104,12 +135,13 @@ def _to_device_mesh(vertices, faces):
             f.to(device=dev, dtype=torch.int32).reshape(-1, 3).contiguous())
 
 
-def compute(vertices, faces, size=128, fix=False, level=0.015, return_mesh=False):
+def compute(vertices, faces, size=128, fix=False, level=0.015, return_mesh=False, sign='parity', beta=0.0):
     """mesh2sdf.compute with its argument order, so tools/repair_mesh.py:150 ports unchanged: ``vertices`` [V, 3] in
     [-1, 1]^3 and ``faces`` [F, 3] (numpy or tensors) -> the signed lattice [S, S, S] as a fp32 device tensor, and with
     ``return_mesh`` also the mesh ``(verts, faces)`` the lattice belongs to, as device tensors.
 
-    fix=False: the signed lattice of the input as it is (parity sign: only meaningful for a watertight input).
+    fix=False: the signed lattice of the input as it is -- ``sign='parity'``: only meaningful for a watertight input;
+      ``sign='winding'``: ``mesh_to_sdf(signed='winding', beta=beta)``, meaningful for a raw mesh too.
     fix=True: the repair, composed from public calls only --
       1. ``u = mesh_to_sdf([input], size, signed=False)``, the unsigned distance;
       2. ``marching_cubes(u, level, bbmin=-1, bbmax=1)``: the surface at distance ``level`` around the input, an outer
@@ -118,9 +150,13 @@ def compute(vertices, faces, size=128, fix=False, level=0.015, return_mesh=False
       4. ``mesh_to_sdf([shell], size, signed=True)``, returned with the shell.
     So the repaired surface lies ``level`` outside the input, as mesh2sdf's does.  See the module docstring for where
     the result can differ from mesh2sdf's (marching-cubes table, components by shared vertex, exact far field)."""
+    if sign not in ('parity', 'winding'):
+        raise ValueError("compute: sign must be 'parity' or 'winding', got %r" % (sign,))
+    if fix and sign != 'parity':
+        raise ValueError('compute: sign=%r needs fix=False (the repaired shell is watertight)' % (sign,))
     m = _to_device_mesh(vertices, faces)
     if not fix:
-        sdf = mesh_to_sdf([m], size, signed=True)[0]
+        sdf = mesh_to_sdf([m], size, signed='winding' if sign == 'winding' else True, beta=beta)[0]
         return (sdf, m) if return_mesh else sdf
     u = mesh_to_sdf([m], size, signed=False)
     shell = mesh.largest_component(mesh.marching_cubes(u, float(level), bbmin=-1, bbmax=1))[0]
@@ -172,7 +208,7 @@ def read_mesh(path):
 
 
 def prepare_mesh(path, name, sdf_dir, mesh_dir, bbox_dir, dataset_dir=None, size=128, level=0.015, points=100000,
-                 seed=0, fix=True):
+                 seed=0, fix=True, sign='parity', beta=0.0):
     """run_mesh2sdf (tools/repair_mesh.py:139-156) for one raw mesh, plus sample_pts_from_mesh (:250-257) with
     ``dataset_dir``: read ``path``, ``normalize`` it, ``compute(fix=True, return_mesh=True)`` and write
       ``sdf_dir/<name>.npy``    the lattice [S, S, S] fp32,
@@ -180,12 +216,13 @@ def prepare_mesh(path, name, sdf_dir, mesh_dir, bbox_dir, dataset_dir=None, size
       ``bbox_dir/<name>.npz``   bbmax, bbmin (of the raw vertices, float64) and mul = 0.8,
       ``dataset_dir/<name>/pointcloud.npz``  ``points`` [n, 3] and ``normals`` [n, 3] fp16 drawn from the saved mesh by
                                 ``metrics.sample_surface(normals=True, normalize=False)`` (seeded: reproducible).
-    Returns the list of files written.  fix=False skips the repair (a mesh known to be watertight)."""
+    Returns the list of files written.  fix=False skips the repair (a mesh known to be watertight); with
+    ``sign='winding'`` it writes the signed lattice of the raw mesh itself, signed by its winding number."""
     v, f = read_mesh(path)
     if len(f) == 0:
         raise ValueError('prepare_mesh: %s has no faces' % path)
     vn, bbmin, bbmax = normalize(v, MESH_SCALE)
-    sdf, (mv, mf) = compute(vn, f, size, fix=fix, level=level, return_mesh=True)
+    sdf, (mv, mf) = compute(vn, f, size, fix=fix, level=level, return_mesh=True, sign=sign, beta=beta)
     mv = mv * SHAPE_SCALE
     files = [os.path.join(sdf_dir, name + '.npy'), os.path.join(mesh_dir, name + '.obj'),
              os.path.join(bbox_dir, name + '.npz')]
@@ -228,6 +265,10 @@ def parser():
     ap.add_argument('--pointcloud', action='store_true', help='also draw the oriented point cloud of the saved mesh')
     ap.add_argument('--points', type=int, default=100000, help='points of the cloud')
     ap.add_argument('--no-fix', action='store_true', help='the input is watertight: take its signed lattice as it is')
+    ap.add_argument('--sign', choices=['parity', 'winding'], default='parity', help="'winding': the signed lattice "
+                    'of the raw mesh itself, signed by its winding number (implies --no-fix)')
+    ap.add_argument('--beta', type=float, default=mesh_query.DEFAULT_CLI_BETA, help='far-field opening of --sign '
+                    'winding (0: exact)')
     ap.add_argument('--seed', type=int, default=0)
     return ap
 
@@ -239,7 +280,8 @@ def main(argv=None):
     for path in args.input:
         prepare_mesh(path, shape_name(path), os.path.join(root, 'sdf'), os.path.join(root, 'mesh'),
                      os.path.join(root, 'bbox'), os.path.join(root, 'dataset') if args.pointcloud else None,
-                     args.size, args.level, args.points, args.seed, fix=not args.no_fix)
+                     args.size, args.level, args.points, args.seed, fix=not (args.no_fix or args.sign == 'winding'),
+                     sign=args.sign, beta=args.beta if args.sign == 'winding' else 0.0)
     print('mesh2sdf: %d shapes written under %s' % (len(args.input), root))
 
 

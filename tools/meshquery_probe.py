@@ -11,7 +11,7 @@ events bracket finished work).  The work the culling leaves is counted by the ke
 (ofx_mesh_query_set_counters, a separate untimed call): bins searched, triangles staged and triangles evaluated per
 wave of 64 queries, against brute force (queries x triangles).
 
-The split of a call into its kernels (tb_init / tb_bound / tb_bin<1, 2> / scan / mq_key / sort / mq_dist / mq_sign) comes from a
+The split of a call into its kernels (tb_init / tb_bound / tb_bin<1, 2> / scan / tb_key / sort / mq_dist / mq_sign) comes from a
 kernel trace taken in a run of its own (--trace-only runs the signed 'both' query once so that the trace is short):
     rocprofv3 --kernel-trace --stats -d profiles/meshquery/trace -- python tools/meshquery_probe.py --trace-only
 
