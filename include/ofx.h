@@ -772,11 +772,16 @@ int ofx_ddim_x0_update(float* x, const float* x0, const float* noise, const floa
  * Triangles: the project's own 256-case table (tools/gen_mc_table.py: ambiguous faces separate their inside corners,
  * so the mesh is closed away from the boundary), ordered by cell linear index then table order, int32 indices into the
  * shape's own vertices, (v1 - v0) x (v2 - v0) toward increasing values.  Output is bitwise reproducible (scans, no
- * atomic appends).  Limits: 2 <= size <= 512 and batch * size^3 * 5 <= INT32_MAX (ofx_mc_ws_bytes returns 0 outside).
+ * atomic appends).  Limits: 2 <= size <= 512, 1 <= batch <= 65535 (the count pass puts the shape into the second grid
+ * dimension, the emit pass launches per shape) and batch * size^3 * 5 <= INT32_MAX; ofx_mc_ws_bytes returns 0 outside
+ * and ofx_mc_count / ofx_mc_emit OFX_EINVAL with nothing launched, as for a NULL pointer or a non-finite level.
+ * t is plain fp32: corners exactly at `level` (and -0.0 at level 0.0) are outside; when v_b - v_a overflows to +-inf
+ * (v_a = -3e38, v_b = 3e38), t is +-0 and the vertex is the owner point a.
  * ofx_mc_count: counts[b*3 + {0,1,2}] = vertices, triangles, cells with a non-finite corner of shape b (int64).
  * ofx_mc_emit: after the caller has read the counts back, writes shape b's vertices at verts + 3 * vert_off[b] and its
- * triangles at faces + 3 * tri_off[b] (offsets: int64 device arrays); ws is the workspace of the count pass (its scans
- * are read, its id map is written), so the two calls must see the same sdf / level.
+ * triangles at faces + 3 * tri_off[b] (offsets: int64 device arrays; the shapes' ranges may leave gaps, which are not
+ * written); ws is the workspace of the count pass (its scans are read, its id map is written), so the two calls must
+ * see the same sdf / level.
  * ofx_mc_table_host (host memory): tri_table [256 * 16] edge ids, -1 padded, ntri [256].  Corner c = dx*4 + dy*2 + dz,
  * edge e = axis*4 + k, k = the owner corner's coordinates on the other two axes (x, y, z order, high bit first). */
 size_t ofx_mc_ws_bytes(int batch, int size);
@@ -833,7 +838,8 @@ int ofx_fieldmesh_emit(int batch, int size, float level, float step, float bbmin
  * ofx_mesh_cc_ws_bytes bytes shared by the calls on one mesh, in the order label, then table (+ stats) or select
  * (+ extract); `status` is two int32 the caller reads back with its counts: status[0] != 0 a capped union-find loop
  * gave up (the results are not to be used), status[1] != 0 a face index outside its shape's [0, n_verts) (bit 0) or
- * inconsistent offsets (bit 1) -- then no later pass touches the mesh.
+ * inconsistent offsets (bit 1) -- then no later pass touches the mesh or writes an output (_table, _stats, _select and
+ * _extract read status[1] on the device and return OFX_OK with every output as the caller left it).
  * Two vertices are connected when a face uses both.  label[v] = the lowest vertex id of v's component within its shape
  * (a vertex that no face uses: itself); components with at least one face are numbered 0 .. K-1 by ascending label.
  * Everything is a function of the mesh alone (integer min / max atomics and scans, no atomic appends): bitwise
@@ -844,13 +850,17 @@ int ofx_fieldmesh_emit(int batch, int size, float level, float step, float bbmin
  *   [batch + 1], the offsets of the shapes' components in the dense numbering (comp_off[batch] = all components).
  * ofx_mesh_cc_stats (:461, the extents' inputs): after _table and the caller's readback of comp_off[batch] = n_comp,
  *   table int32 [n_comp, 8]: columns 0-2 / 3-5 the fp32 bits of the exact bounding-box min / max, 6 the vertex
- *   count, 7 the face count.
+ *   count, 7 the face count.  The order of the box is that of the bit patterns: -0.0 lies below +0.0 (a component
+ *   holding both has min -0.0 and max +0.0), denormals and the infinities are ordinary values.  n_comp may be smaller
+ *   than the true count: the first n_comp components are written and nothing else; n_comp == 0 writes nothing.
  * ofx_mesh_cc_select (:461-465): per shape the component with the largest max-axis extent (fp32 subtraction of the
  *   stored coordinates), a tie to the lowest label; winner_label int32 [batch] (-1: no face); keep_counts int64
  *   [3 * batch]: kept vertices, kept faces, components before cleaning.  Needs neither _table nor _stats.
  * ofx_mesh_cc_extract (:466): after the caller has read keep_counts back, writes shape b's kept vertices at out_verts +
- *   3 * new_vert_off[b] and kept faces, renumbered, at out_faces + 3 * new_tri_off[b], both in their original order; ws
- *   is the workspace ofx_mesh_cc_select left. */
+ *   3 * new_vert_off[b] and kept faces, renumbered, at out_faces + 3 * new_tri_off[b], both in their original order
+ *   (the shapes' ranges may leave gaps, which are not written); ws is the workspace ofx_mesh_cc_select left.
+ * OFX_EINVAL with nothing launched for totals or a batch outside the limits or a NULL pointer (comp_of_vert excepted;
+ * table may be NULL only with n_comp == 0). */
 size_t ofx_mesh_cc_ws_bytes(int64_t total_verts, int64_t total_faces, int batch);
 int ofx_mesh_cc_label(const int32_t* faces, const int64_t* vert_off, const int64_t* tri_off, int batch,
                       int64_t total_verts, int64_t total_faces, int32_t* label, void* ws, int32_t* status,
@@ -877,20 +887,27 @@ int ofx_mesh_cc_extract(const float* verts, const int32_t* faces, const int64_t*
  * 1 <= total_faces <= INT32_MAX / 3 (ofx_simplify_ws_bytes returns 0 outside).  `ws` is one workspace of
  * ofx_simplify_ws_bytes bytes shared by the two calls; `status` is two int32 the caller reads back with the counts:
  * status[0] != 0 a face index outside its shape's [0, n_verts) (bit 0) or inconsistent offsets (bit 1) -- checked
- * before any index is followed, and then no later pass touches the mesh; status[1] != 0 a vertex needs a cell index
- * >= 1024 under cell_size (the outputs are not to be used).  Nothing allocates, nothing synchronises, no
+ * before any index is followed, and then no later pass touches the mesh; status[1] bit 0 a vertex needs a cell index
+ * >= 1024 under cell_size, bit 1 a shape has a NaN or infinite vertex coordinate (in a vertex a face uses or not, under
+ * `cells` and under cell_size alike); the outputs of the flagged shapes (counts columns 6 / 7) are not to be used,
+ * those of the other shapes are what they would be alone.  Nothing allocates, nothing synchronises, no
  * floating-point atomics: the output is a function of each shape's own vertices and faces, bitwise reproducible, the
  * same alone or anywhere in a batch.
  * ofx_simplify_cluster: the grid is `cells` (1 .. 1024) cells along the longest side of each shape's bounding box, or,
  *   with cells == 0, cells of side cell_size (finite, > 0); 0 < reg <= 1 is the regulariser of the placement.  All
  *   arithmetic is fp64.  counts int64 [batch, 8]: occupied cells (clusters), kept vertices, kept faces, faces that
  *   collapsed (fewer than three different clusters), faces dropped as duplicates of an earlier face, 1 if the shape
- *   has a bad face index, 1 if it overflows the grid, 0.  `stages` = ofx_simplify_stages() runs everything; a smaller
- *   value stops after that many of {keys, vertex sort, incidence sort, solve, face pass} (for timing the split; the
- *   counts are then incomplete).
+ *   has a bad face index, 1 if it overflows the grid, 1 if it has a non-finite vertex (it is then left as a single
+ *   cluster and never flagged as overflowing).  `stages` = ofx_simplify_stages() runs everything; a smaller value
+ *   >= 1 stops after that many of {keys, vertex sort, incidence sort, solve, face pass} (for timing the split):
+ *   status and the columns 5-7 are complete from stage 1 on, the columns 0-4 are 0 until the face pass has run.
+ *   OFX_EINVAL with nothing launched (counts and status as the caller left them) for stages < 1 or >
+ *   ofx_simplify_stages(), cells outside [0, 1024], cells == 0 with a cell_size that is not finite and > 0, reg
+ *   outside (0, 1] or NaN, totals or a batch outside the limits, a NULL pointer.
  * ofx_simplify_extract: after the caller has read counts back, writes shape b's kept cluster positions (rounded once
  *   to fp32, in ascending (ix, iy, iz) cell order) at out_verts + 3 * new_vert_off[b] and its kept faces (input order,
- *   rotated so that the lowest cluster comes first, renumbered) at out_faces + 3 * new_tri_off[b]. */
+ *   rotated so that the lowest cluster comes first, renumbered) at out_faces + 3 * new_tri_off[b] (the shapes'
+ *   ranges may leave gaps, which are not written). */
 int ofx_simplify_stages(void);
 size_t ofx_simplify_ws_bytes(int64_t total_verts, int64_t total_faces, int batch);
 int ofx_simplify_cluster(const float* verts, const int32_t* faces, const int64_t* vert_off, const int64_t* tri_off,
@@ -921,8 +938,10 @@ int ofx_simplify_extract(const int32_t* faces, const int64_t* vert_off, const in
  *   in its corner order.  Welded: every lattice corner a quad uses once, in ascending corner index
  *   (cx*(R+1) + cy)*(R+1) + cz.  Coordinates corner * (2 / R) - 1, exact in fp32.
  * Output is bitwise reproducible (popcounts and scans; the only atomics are the ORs into the bitmasks).  `weld` must be
- * the same for ws_bytes, count and emit.  Limits: batch * R^3 * 24 <= INT32_MAX (ofx_voxmesh_ws_bytes returns 0
- * outside, which excludes depth 9). */
+ * the same for ws_bytes, count and emit.  Limits: 1 <= batch <= 65535 (the dense fill puts the shape into the second
+ * grid dimension) and batch * R^3 * 24 <= INT32_MAX (ofx_voxmesh_ws_bytes returns 0 outside, which excludes depth 9;
+ * the other entries return OFX_EINVAL with nothing launched, as for a NULL pointer, n < 0, batch0 < 0 or a NaN
+ * threshold).  The offsets of _emit may leave gaps between the shapes' ranges, which are not written. */
 size_t ofx_voxmesh_ws_bytes(int batch, int depth, int weld);
 int ofx_voxmesh_mask_keys(const int64_t* keys, int64_t n, int batch0, int batch, int depth, void* ws, void* stream);
 int ofx_voxmesh_mask_dense(const float* occ, int batch, int depth, float threshold, void* ws, void* stream);

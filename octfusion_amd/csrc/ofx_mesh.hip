@@ -5,6 +5,10 @@
 // inside iff v < level.  One vertex per lattice edge with exactly one inside endpoint, owned by the lower endpoint and
 // numbered by (owner linear index, axis x/y/z); triangles from the table of tools/gen_mc_table.py, numbered by (cell
 // linear index, table order).  Order comes from scans, never from atomics: the output is bitwise reproducible.
+// Limits: 2 <= size <= 512, 1 <= batch <= 65535 (the second grid dimension of the count pass) and
+// batch * size^3 * 5 <= INT32_MAX; ofx_mc_ws_bytes returns 0 and the entries OFX_EINVAL outside.  The crossing
+// parameter t = (level - v0) / (v1 - v0) is plain fp32: when v1 - v0 overflows to +-inf, t is +-0 and the vertex is the
+// owner point.
 //
 // Passes.  The lattice is cut into chunks of MC_CHUNK consecutive points (one block each).
 //   count  (ofx_mc_count): every block counts its vertices, triangles and non-finite cells -> three int32 per block;
@@ -28,6 +32,7 @@ constexpr int MC_T = 256;                 // threads per block (4 waves)
 constexpr int MC_ITER = 4;                // points per thread
 constexpr int MC_CHUNK = MC_T * MC_ITER;  // points per block
 constexpr int MC_MAX_SIZE = 512;          // id map: 29-bit vertex id + 3-bit crossing mask; 3 * 512^3 < 2^29
+constexpr int MC_MAX_BATCH = 65535;       // the count pass puts the shape into the grid's y dimension
 constexpr uint32_t MC_ID_MASK = (1u << 29) - 1;
 
 struct McWs {
@@ -59,8 +64,9 @@ size_t mc_layout(int batch, int size, char* base, McWs* w) {
 }
 
 bool mc_valid(int batch, int size) {
-  // every count of the batch goes through one int32 scan: bound the worst case (5 triangles per cell)
-  return batch >= 1 && size >= 2 && size <= MC_MAX_SIZE &&
+  // every count of the batch goes through one int32 scan: bound the worst case (5 triangles per cell); the batch is
+  // a grid dimension of the count pass (and the emit pass launches per shape), so small lattices are bounded by it
+  return batch >= 1 && batch <= MC_MAX_BATCH && size >= 2 && size <= MC_MAX_SIZE &&
          (int64_t)batch * size * size * size * OFX_MC_MAX_TRI <= INT32_MAX;
 }
 

@@ -376,7 +376,8 @@ __global__ __launch_bounds__(CC_T) void cc_select_kernel(const int32_t* __restri
   }
 }
 
-// winner labels, the component counts (before the keep scan reuses `pre`) -- one small block
+// winner labels, the component counts (before the keep scan reuses `pre`) -- one small block.  This kernel and
+// cc_counts_kernel write all of keep_counts, and only when status[1] is clear.
 __global__ void cc_winner_kernel(const unsigned long long* __restrict__ key, const int32_t* __restrict__ pre,
                                  const int64_t* __restrict__ vert_off, int batch,
                                  int32_t* __restrict__ winner_label, int64_t* __restrict__ keep_counts,
@@ -554,7 +555,6 @@ extern "C" int ofx_mesh_cc_select(const float* verts, const int32_t* faces, cons
   rc = cc_rows(verts, faces, label, vert_off, tri_off, batch, V, F, rows, CC_ROW_SEL, w.tab, w, status, st);
   if (rc) return rc;
   if (hipMemsetAsync(w.key, 0, (size_t)batch * 8, st) != hipSuccess) return OFX_ELAUNCH;
-  if (hipMemsetAsync(keep_counts, 0, (size_t)batch * 3 * 8, st) != hipSuccess) return OFX_ELAUNCH;
   cc_select_kernel<<<ofx_grid(V, CC_T), CC_T, 0, st>>>(label, w.flag, w.pre, w.tab, vert_off, batch, V, rows, w.key,
                                                       status);
   cc_winner_kernel<<<1, CC_T, 0, st>>>(w.key, w.pre, vert_off, batch, winner_label, keep_counts, status);

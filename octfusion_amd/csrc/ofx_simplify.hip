@@ -11,7 +11,9 @@
 // must agree with numpy exactly).
 //   grid      lo / hi = exact min / max of ALL vertices of the shape, side = max axis of hi - lo, h = side / cells or
 //             h = cell_size; cell = floor((v - lo) / h), clamped to cells - 1 (cells) or flagged >= 1024 (cell_size);
-//             side == 0: cell (0, 0, 0)
+//             side == 0: cell (0, 0, 0).  A shape with a NaN or infinite coordinate in ANY of its vertices (used by a
+//             face or not) is refused in both modes: bit 1 of status[1], counts column 7; it is left as one cluster
+//             in cell (0, 0, 0) and its outputs are not to be used; the other shapes of the batch are not affected
 //   clusters  occupied cells in ascending (ix, iy, iz); m = mean of the cluster's vertices, c = lo + (cell + 0.5) h
 //   quadrics  face t, once per distinct cluster k of its corners: q_i = p_i - c_k, n = (q1 - q0) x (q2 - q0),
 //             A_k += n n^T, b_k += (n . q0) n
@@ -23,7 +25,8 @@
 //
 // Passes (g = vert_off[b] + v; every pass after `check` returns at once when a face index is out of range):
 //   keys      check F; box V (order-preserving uint32 min / max atomics, one set per 1024-vertex chunk in one shape);
-//             grid B; key[g] = b << 30 | ix << 20 | iy << 10 | iz
+//             grid B (a box entry that is not finite <=> a non-finite vertex: the encoding sorts NaN outside the
+//             infinities); key[g] = b << 30 | ix << 20 | iy << 10 | iz
 //   vsort     stable radix sort of (key, g) over the live bits; head flags + scan -> cluster id of every vertex (global,
 //             ascending in (shape, cell)), cluster start in the sorted order, clusters before every shape
 //   isort     per face three (cluster, face) slots, repeats replaced by a sentinel that sorts last; stable radix sort by
@@ -50,7 +53,8 @@ namespace {
 
 constexpr int SP_T = 256;
 constexpr int SP_MAX_CELLS = 1024;
-constexpr int SP_COUNTS = 8;     // clusters, kept vertices, kept faces, collapsed, duplicate, bad index, overflow, -
+constexpr int SP_COUNTS = 8;     // clusters, kept vertices, kept faces, collapsed, duplicate, bad index, overflow,
+                                 // non-finite vertex
 constexpr int SP_GRID = 5;       // lo[3], h, side
 constexpr int SP_STAGES = 5;
 
@@ -270,11 +274,22 @@ __global__ __launch_bounds__(SP_T) void sp_box_kernel(const float* __restrict__ 
 
 __global__ void sp_grid_kernel(const uint32_t* __restrict__ box, const int64_t* __restrict__ vert_off, int batch,
                                int cells, double cell_size, double* __restrict__ grid,
-                               const int32_t* __restrict__ status) {
+                               int64_t* __restrict__ counts, int32_t* status) {
   if (status[0]) return;
   SP_LOOP(b, batch) {
     double* gr = grid + b * SP_GRID;
     if (vert_off[b + 1] == vert_off[b]) {
+      for (int a = 0; a < SP_GRID; ++a) gr[a] = 0.0;
+      continue;
+    }
+    // Every vertex of the shape went into the box, and the encoding puts -NaN below -inf and +NaN above +inf: the
+    // shape has a non-finite coordinate iff one of its six box entries is not finite.
+    bool finite = true;
+#pragma unroll
+    for (int a = 0; a < 6; ++a) finite = finite && isfinite(sp_dec(box[b * 6 + a]));
+    if (!finite) {                     // refused: flagged, and left as one cluster in cell (0, 0, 0) (side == 0)
+      atomicOr(status + 1, 2);
+      counts[b * SP_COUNTS + 7] = 1;
       for (int a = 0; a < SP_GRID; ++a) gr[a] = 0.0;
       continue;
     }
@@ -707,7 +722,8 @@ extern "C" int ofx_simplify_cluster(const float* verts, const int32_t* faces, co
   sp_check_kernel<<<ofx_grid(F, SP_T), SP_T, 0, st>>>(faces, vert_off, tri_off, batch, V, F, counts, status);
   sp_box_init_kernel<<<ofx_grid((int64_t)batch * 6, SP_T), SP_T, 0, st>>>(w.box, batch);
   sp_box_kernel<<<ofx_grid(ofx_cdiv(V, SP_BOX_CHUNK / 64), SP_T), SP_T, 0, st>>>(verts, vert_off, batch, V, w.box, status);
-  sp_grid_kernel<<<ofx_grid(batch, SP_T), SP_T, 0, st>>>(w.box, vert_off, batch, cells, cell_size, w.grid, status);
+  sp_grid_kernel<<<ofx_grid(batch, SP_T), SP_T, 0, st>>>(w.box, vert_off, batch, cells, cell_size, w.grid, counts,
+                                                        status);
   sp_keys_kernel<<<ofx_grid(V, SP_T), SP_T, 0, st>>>(verts, vert_off, batch, V, cells, w.grid, w.key_a, w.idx_a,
                                                     counts, status);
   OFX_LAUNCH_CHECK();

@@ -7,7 +7,9 @@
 // is the reference's emission order (np.where).  Faces of a cell in the order +z, -z, -x, +x, +y, -y; a face is exposed
 // when the neighbour bit is clear or the cell lies on the grid boundary (the reference pads with zeros).  Order comes
 // from popcounts and scans, never from atomics: the output is bitwise reproducible.  The only atomics are the
-// order-independent atomicOr of the two bitmasks.
+// order-independent atomicOr of the two bitmasks.  Limits: 1 <= depth <= 9, 1 <= batch <= 65535 (the second grid
+// dimension of the dense fill) and batch * R^3 * 24 <= INT32_MAX; ofx_voxmesh_ws_bytes returns 0 and the entries
+// OFX_EINVAL outside.
 //
 // Passes.
 //   fill   (ofx_voxmesh_mask_keys / _mask_dense): octree keys are decoded and set with atomicOr on a cleared mask;
@@ -30,6 +32,7 @@ namespace {
 constexpr int VM_T = 256;          // threads per block (4 waves)
 constexpr int VM_MAX_DEPTH = 9;
 constexpr int VM_BOUND = 24;       // batch * R^3 * 24 <= INT32_MAX: 6 quads = 12 triangles = 24 unwelded vertices a cell
+constexpr int VM_MAX_BATCH = 65535;  // the dense fill puts the shape into the grid's y dimension
 
 // Faces in emission order +z, -z, -x, +x, +y, -y.  VM_QUAD: the four corners of the face, 4 bits each, corner code
 // dx*4 + dy*2 + dz, first corner in the low bits.  VM_TRI: two triangles, six 2-bit indices into those four corners.
@@ -59,7 +62,8 @@ inline int64_t vm_ncw(int depth) {
 }
 
 bool vm_valid(int batch, int depth) {
-  return batch >= 1 && depth >= 1 && depth <= VM_MAX_DEPTH && (int64_t)batch * vm_cells(depth) * VM_BOUND <= INT32_MAX;
+  return batch >= 1 && batch <= VM_MAX_BATCH && depth >= 1 && depth <= VM_MAX_DEPTH &&
+         (int64_t)batch * vm_cells(depth) * VM_BOUND <= INT32_MAX;
 }
 
 size_t vm_layout(int batch, int depth, bool weld, char* base, VmWs* w) {

@@ -31,6 +31,7 @@ MESH_SCALES = {'snet_uncond': 0.5, 'snet_cond': 0.5, 'obja_uncond': 1.0}
 
 MAX_SIZE = 512          # csrc/ofx_mesh.hip: the id map packs a 29-bit vertex id
 MAX_TRI_PER_CELL = 5    # every count of one call goes through one int32 scan (include/ofx.h)
+MAX_BATCH = 65535       # shapes per call of the library (include/ofx.h: a grid dimension of the count pass)
 
 
 def mesh_scale(config):
@@ -39,7 +40,7 @@ def mesh_scale(config):
 
 
 def _max_batch(size):
-    return max(1, (2 ** 31 - 1) // (MAX_TRI_PER_CELL * size ** 3))
+    return min(MAX_BATCH, max(1, (2 ** 31 - 1) // (MAX_TRI_PER_CELL * size ** 3)))
 
 
 def marching_cubes(sdfs, level=0.0, bbmin=-0.9, bbmax=0.9, scale=1.0, clean=False, stats=None):
@@ -50,7 +51,7 @@ def marching_cubes(sdfs, level=0.0, bbmin=-0.9, bbmax=0.9, scale=1.0, clean=Fals
     negative inside).
 
     Makes ONE host synchronisation: the per-shape counts are read back between the count and the emit pass (once
-    per group of ``(2^31 - 1) // (5 R^3)`` shapes -- 25 at R = 256).  Raises ValueError naming the shape if a cell
+    per group of ``min(65535, (2^31 - 1) // (5 R^3))`` shapes -- 25 at R = 256).  Raises ValueError naming the shape if a cell
     of it has a non-finite corner, and OfxError without a GPU (there is no CPU path).
 
     clean=True keeps only each shape's largest component (the reference's export_mesh clean=True; what

@@ -87,13 +87,15 @@ def _simplify_group(verts, faces, nv, nf, first, cells, cell_size, reg, stages=N
     if stages is not None:                             # a timing run of the first stages: nothing to read
         return None, None
     host = torch.cat([counts, status.to(torch.int64)]).cpu()          # the host sync
-    bad, over = int(host[-2]), int(host[-1])
+    bad, over = int(host[-2]), int(host[-1])       # over: bit 0 a grid overflow, bit 1 a non-finite vertex
     c = host[:-2].view(B, 8)
     if bad & 2:
         raise ValueError('simplify: inconsistent offsets')
     if bad:
         raise ValueError('simplify: shape %d has a face index outside [0, V)'
                          % (first + int(torch.nonzero(c[:, 5])[0])))
+    if over & 2:
+        raise ValueError('simplify: shape %d has a non-finite vertex' % (first + int(torch.nonzero(c[:, 7])[0])))
     if over:
         raise ValueError('simplify: shape %d needs %d or more cells of size %g along an axis'
                          % (first + int(torch.nonzero(c[:, 6])[0]), MAX_CELLS, cell_size))
@@ -132,8 +134,9 @@ def simplify(meshes, cells=None, cell_size=None, reg=1e-3, stats=None):
 
     One host synchronisation per group of meshes (the kept counts and the status words; the workspace is sized from V
     and F).  Raises ValueError for a wrong dtype, device or argument before any launch, ValueError naming the shape for
-    a face index outside ``[0, V)`` (checked on the device before anything follows an index) or a grid overflow, after
-    the readback, and OfxError without a GPU (there is no CPU path)."""
+    a face index outside ``[0, V)`` (checked on the device before anything follows an index), a NaN or infinite vertex
+    coordinate (whether a face uses the vertex or not, under ``cells`` and ``cell_size`` alike) or a grid overflow,
+    after the readback, and OfxError without a GPU (there is no CPU path)."""
     _lib.require_device()
     meshes = mesh._check_meshes(meshes, 'simplify')
     _check_args(cells, cell_size, reg)

@@ -12,10 +12,11 @@ from . import _lib
 
 MAX_DEPTH = 8           # include/ofx.h: batch * R^3 * 24 <= INT32_MAX leaves no room for depth 9
 _BOUND = 24             # 6 quads = 12 triangles = 24 unwelded vertices per cell through one int32 scan
+MAX_BATCH = 65535       # shapes per call of the library (include/ofx.h: a grid dimension of the dense fill)
 
 
 def _max_batch(R):
-    return max(1, (2 ** 31 - 1) // (_BOUND * R ** 3))
+    return min(MAX_BATCH, max(1, (2 ** 31 - 1) // (_BOUND * R ** 3)))
 
 
 def _depth_of(R, who):
@@ -37,8 +38,8 @@ def voxel_mesh(occ, threshold=0.4, weld=True):
     fp32); quads in the reference's order: cells ascending in (x, y, z), within a cell +z, -z, -x, +x, +y, -y.  An
     empty grid gives empty tensors.  Bitwise reproducible.
 
-    ONE host synchronisation per group of ``(2^31 - 1) // (24 R^3)`` shapes (the per-shape counts, read back between
-    the count and the emit pass).  Raises ValueError for a wrong dtype, device or shape or a non-power-of-two R, and
+    ONE host synchronisation per group of ``min(65535, (2^31 - 1) // (24 R^3))`` shapes (the per-shape counts, read
+    back between the count and the emit pass).  Raises ValueError for a wrong dtype, device or shape or a non-power-of-two R, and
     OfxError without a GPU (there is no CPU path).
 
     Choices:

@@ -3,7 +3,8 @@ largest_component): the reference's export_mesh(clean=True), models/octfusion_mo
 
   * two vertices are connected when a face uses both; components are numbered by their lowest vertex id, and only
     components with a face count (a vertex no face uses has component -1);
-  * the table holds exact fp32 bounding boxes and exact counts;
+  * the table holds exact fp32 bounding boxes and exact counts; the box is ordered by bit pattern (`order_key`): -0.0
+    lies below +0.0, denormals and the infinities are ordinary values;
   * the winner has the largest max-axis extent, computed in fp32; np.argmax gives a tie to the first component;
   * extraction keeps vertices and faces in their order and renumbers the indices.
 """
@@ -77,6 +78,18 @@ def refines(fine, coarse):
     return len(pairs) == len(np.unique(fine))
 
 
+def order_key(x):
+    """Order-preserving uint32 image of fp32 values, as the device's integer min / max use it: -0.0 below +0.0."""
+    u = np.ascontiguousarray(np.asarray(x, np.float32)).view(np.uint32)
+    return np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000)).astype(np.uint32)
+
+
+def order_value(e):
+    e = np.asarray(e, np.uint32)
+    u = np.where(e & np.uint32(0x80000000), e ^ np.uint32(0x80000000), ~e).astype(np.uint32)
+    return u.view(np.float32)
+
+
 def table(verts, faces):
     """dict: comp_of_vert [V], comp_of_face [F], bbox_min / bbox_max fp32 [K, 3], n_verts / n_faces int64 [K]."""
     v = np.asarray(verts, np.float32).reshape(-1, 3)
@@ -91,8 +104,9 @@ def table(verts, faces):
     nverts = np.bincount(cv[used], minlength=K).astype(np.int64)
     if K:
         start = np.concatenate([[0], np.cumsum(nverts)[:-1]])
-        bmin = np.minimum.reduceat(v[idx], start, axis=0)
-        bmax = np.maximum.reduceat(v[idx], start, axis=0)
+        keys = order_key(v[idx])
+        bmin = order_value(np.minimum.reduceat(keys, start, axis=0))
+        bmax = order_value(np.maximum.reduceat(keys, start, axis=0))
     else:
         bmin = bmax = np.zeros((0, 3), np.float32)
     return dict(comp_of_vert=cv, comp_of_face=cf, bbox_min=bmin.astype(np.float32), bbox_max=bmax.astype(np.float32),
@@ -100,8 +114,9 @@ def table(verts, faces):
 
 
 def extents(tab):
-    return (tab['bbox_max'] - tab['bbox_min']).astype(np.float32).max(axis=1) if len(tab['n_verts']) else \
-        np.zeros(0, np.float32)
+    with np.errstate(over='ignore', invalid='ignore'):
+        return (tab['bbox_max'] - tab['bbox_min']).astype(np.float32).max(axis=1) if len(tab['n_verts']) else \
+            np.zeros(0, np.float32)
 
 
 def select(tab):

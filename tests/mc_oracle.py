@@ -2,7 +2,8 @@
 
   * cell (i, j, k), 0 <= i, j, k < R-1; a corner is inside iff v < level; the lattice boundary is not padded;
   * one vertex per lattice edge with exactly one inside endpoint, owned by its lower endpoint a, running +x / +y / +z
-    to b; index-space position a + t (b - a), t = (level - v_a) / (v_b - v_a) in fp32; output (p * step + bbmin) *
+    to b; index-space position a + t (b - a), t = (level - v_a) / (v_b - v_a) in fp32 (a difference that overflows
+    to +-inf gives t = +-0: the vertex is the owner point); output (p * step + bbmin) *
     scale with step = (bbmax - bbmin) / R; vertex order: owner's linear index (x slowest), then axis x, y, z;
   * triangles from the table of tools/gen_mc_table.py, ordered by cell linear index, then table order; int32,
     0-based into the shape's own vertices.
@@ -72,7 +73,9 @@ def marching_cubes(sdf, level=0.0, bbmin=-0.9, bbmax=0.9, scale=1.0):
     stride = np.array([R * R, R, 1], np.int64)
     vf = v.reshape(-1)
     va, vb = vf[p], vf[p + stride[a]]
-    t = ((lev - va) / (vb - va)).astype(np.float32)
+    assert va.dtype == vb.dtype == np.float32 and lev.dtype == np.float32      # every operation below rounds to fp32
+    with np.errstate(over='ignore'):
+        t = ((lev - va) / (vb - va)).astype(np.float32)
     pos = np.stack([p // (R * R), (p // R) % R, p % R], 1).astype(np.float32)
     pos[np.arange(len(p)), a] += t
     step = np.float32((bbmax - bbmin) / R)

@@ -3,7 +3,8 @@ section 4.16).  float64 throughout; the output positions are rounded once to fp3
 
   1. grid      lo / hi = exact per-axis min / max of ALL vertices, side = max axis of hi - lo; h = side / cells or
                h = cell_size; cell = floor((v - lo) / h) per axis, clamped to cells - 1 under `cells`, an index >= 1024
-               an error under `cell_size`; side == 0: everything in cell (0, 0, 0).
+               an error under `cell_size`; side == 0: everything in cell (0, 0, 0).  A NaN or infinite coordinate in
+               ANY vertex (used by a face or not) is an error in both modes (`nonfinite`).
   2. clusters  one per occupied cell, numbered in ascending (ix, iy, iz); m = mean of its vertices (summed in ascending
                vertex id); c = lo + (cell + 0.5) h.
   3. quadrics  face (p0, p1, p2), once for each distinct cluster k among its corners: q_i = p_i - c_k,
@@ -19,10 +20,18 @@ import numpy as np
 MAX_CELLS = 1024
 
 
+def nonfinite(verts):
+    """True iff a coordinate of any vertex is NaN or infinite: the device flags the shape (status[1] bit 1, counts
+    column 7) and simplify raises."""
+    return not bool(np.isfinite(np.asarray(verts, np.float32)).all())
+
+
 def grid(verts, cells=None, cell_size=None):
     """(lo [3], h, cell [V, 3] int64) of one mesh's vertices."""
     if (cells is None) == (cell_size is None):
         raise ValueError('exactly one of cells and cell_size')
+    if nonfinite(verts):
+        raise ValueError('non-finite vertex')
     v = np.asarray(verts, np.float32).astype(np.float64).reshape(-1, 3)
     lo, hi = v.min(0), v.max(0)
     side = float((hi - lo).max())
