@@ -1256,6 +1256,93 @@ int ofx_ray_scan(const float* verts, const int32_t* faces, const int64_t* vert_o
                  const int32_t* face, float sigma, uint64_t seed, float* points, float* normals, int64_t* out_off,
                  void* ws, void* stream);
 
+/* ------------------------------------------------------------------ mesh checks (csrc/ofx_meshcheck.hip)
+ * Is a mesh sound: weld equal vertices, count what makes it closed, manifold and oriented, find the faces that
+ * intersect other faces.  tests/meshcheck_oracle.py restates the contract in float64.  Meshes concatenated as for
+ * ofx_mesh_query (verts, faces, vert_off, tri_off; batch in [1, 65535]); status [batch] int32 under its conditions: a
+ * face index outside [0, V_b) or a non-finite vertex used by a face gives a non-zero word, that shape's outputs are
+ * left unwritten and nothing is read through such an index.  A shape needs >= 1 face (the caller checks).  Limits of
+ * _weld and _topology: 1 <= total_verts <= 2^30, 1 <= total_faces <= 2^30 / 3; of _selfx: those of ofx_mesh_query.  A
+ * *_ws_bytes function returns 0 outside them; bad arguments give OFX_EINVAL with nothing launched.  No floating-point
+ * atomics; integer atomics only count.  Every output is a pure function of each shape's own arrays, bitwise, alone or
+ * anywhere in a batch, from run to run.
+ *
+ * ofx_mesh_weld: two vertices of a shape are equal iff their three coordinates are equal as fp32 values (-0 == +0);
+ *   a vertex with a non-finite coordinate equals no other.  rep [V] int32 = the lowest index, within the shape, of
+ *   the vertices equal to this one; distinct [batch] int64 = the number of representatives.  No tolerance.
+ * ofx_mesh_weld_extract: after the caller has read `distinct` (and the status words) back.  With n_b the
+ *   representatives of the shapes before b whose status is zero: out_verts [sum distinct, 3] holds shape b's
+ *   representatives from row n_b on, in ascending index, with their stored bits; index [V] int32 = the new index,
+ *   within the shape, of every vertex's representative; out_faces [F, 3] = the faces through index, same count and
+ *   order (a face that has become degenerate stays).  rep and status are ofx_mesh_weld's; ws may be another buffer.
+ *
+ * ofx_mesh_topology: counts [batch, OFX_MESH_TOPOLOGY_K] int64, sums [batch, 2] fp64, edge_faces [F, 3] int32 (may
+ *   be NULL).  A face with fewer than three different indices is index-degenerate: it is counted (column 0) and takes
+ *   no part in anything else below, nor in ofx_mesh_selfx.  Over the other faces:
+ *   1 edges         distinct unordered vertex pairs {face[k], face[(k + 1) % 3]};
+ *   2 boundary      edges used by exactly 1 face;  3 non-manifold  edges used by 3 or more faces;
+ *   4 inconsistent  edges used by exactly 2 faces that both walk them in the same direction;
+ *   5 duplicate     faces whose vertex set equals that of a lower-indexed face, in either orientation (they still
+ *                   count towards the edges);
+ *   6 zero area     faces whose fp64 (b - a) x (c - a) is exactly zero, ofx_mesh_winding's rule;
+ *   7 unreferenced  vertices that none of these faces uses;
+ *   8 components    ofx_mesh_cc_label / _table's count (two vertices are connected when any face uses both); -1 for
+ *                   every shape of the call if those passes refused it or gave up.
+ *   edge_faces[f, k] = the number of faces on the edge leaving corner k of face f, negated where the edge is
+ *   inconsistent; 0 for an index-degenerate face.
+ *   sums: area = sum of |(b - a) x (c - a)| / 2 as 0.5 sqrt((nx nx + ny ny) + nz nz), volume = sum of
+ *   (a . (b x c)) / 6, dots as (x x + y y) + z z, every operation in fp64 rounded on its own; index-degenerate faces
+ *   add 0.  Added in face-index order 64 at a time (the 64 values in a fixed tree, the chunks in turn).
+ *
+ * ofx_mesh_selfx: partners [F] int32 = the number of other faces of its shape a face intersects, first [F] int32 =
+ *   the lowest such face (-1: none), pairs [batch] int64 = sum of partners / 2.  max_faces = the largest face count
+ *   of one shape (host-known: the grid); bins as for ofx_mesh_query (0 = its automatic rule, 1 .. 16; same grid).
+ *   Faces i < j are a candidate pair iff neither is index-degenerate, neither has zero area (above) and their closed
+ *   fp32 bounding boxes overlap -- the box test is part of the definition, so no culling can change an answer.
+ *   Vertices are taken in the stored order of a face and the lower-indexed face is always "i".  All arithmetic is
+ *   fp64 on the fp32 coordinates, every operation rounded on its own; n(T) = (b - a) x (c - a) with differences
+ *   first, plane(T, x) = n(T) . (x - a), dots as above.  dom(T) = the axis of the largest |n(T)| component (the
+ *   lowest among equals); the projection along it keeps axes dom + 1 and dom + 2 (mod 3) as (x, y); o2(p, q, r) =
+ *   the sign of det(qx - px, ry - py, qy - py, rx - px), det(a, b, c, d) = a b - c d in Kahan's fma form (ms_det2),
+ *   whose sign is exact.  With k vertex INDICES in common:
+ *   k = 3  never a pair (duplicates are column 5 above).
+ *   k = 2  with a the corner of i that j does not share, u and v the corners after it in i's cyclic order, b the
+ *          corner of j that i does not share: iff plane(i, b) == 0 and, projected along dom(i), o2(u, v, a) ==
+ *          o2(u, v, b) != 0 -- folded flat onto its neighbour.  Any other dihedral angle is no intersection.
+ *   k = 1  iff the edge of i opposite the shared corner (the two corners after it, in order) meets j, or the same
+ *          edge of j meets i.
+ *   k = 0  iff an edge (corners 0-1, 1-2, 2-0) of i meets j, or one of j meets i.
+ *   The edge p q meets the closed triangle T = a b c: sp, sq = the signs of plane(T, p), plane(T, q).  Equal and
+ *   non-zero: no.  Both zero: projected along dom(T), iff p or q is inside (o2(a, b, x), o2(b, c, x), o2(c, a, x) all
+ *   >= 0 or all <= 0) or p q crosses a b, b c or c a, where p q crosses r s iff d1 d2 <= 0 and d3 d4 <= 0 for d1 =
+ *   o2(p, q, r), d2 = o2(p, q, s), d3 = o2(r, s, p), d4 = o2(r, s, q), except that four zeros (collinear) cross iff
+ *   the closed intervals of the two segments overlap on the axis where |q - p| is larger (x on a tie).  Otherwise:
+ *   with d = q - p, A = a - p, B = b - p, C = c - p, iff d . (A x B), d . (B x C), d . (C x A) are all >= 0 or all
+ *   <= 0.  Touching counts: on an unwelded soup every neighbour is a partner.
+ *   Not detected: bow-tie vertices; nothing is repaired.  ws holds the shared triangle bins (40 bytes per face). */
+#define OFX_MESH_TOPOLOGY_K 9
+size_t ofx_mesh_weld_ws_bytes(int batch, int64_t total_verts, int64_t total_faces);
+int ofx_mesh_weld(const float* verts, const int32_t* faces, const int64_t* vert_off, const int64_t* tri_off, int batch,
+                  int64_t total_verts, int64_t total_faces, int32_t* rep, int64_t* distinct, void* ws, int32_t* status,
+                  void* stream);
+int ofx_mesh_weld_extract(const float* verts, const int32_t* faces, const int64_t* vert_off, const int64_t* tri_off,
+                          int batch, int64_t total_verts, int64_t total_faces, const int32_t* rep,
+                          const int32_t* status, float* out_verts, int32_t* out_faces, int32_t* index, void* ws,
+                          void* stream);
+size_t ofx_mesh_topology_ws_bytes(int batch, int64_t total_verts, int64_t total_faces);
+int ofx_mesh_topology(const float* verts, const int32_t* faces, const int64_t* vert_off, const int64_t* tri_off,
+                      int batch, int64_t total_verts, int64_t total_faces, int64_t* counts, double* sums,
+                      int32_t* edge_faces, void* ws, int32_t* status, void* stream);
+size_t ofx_mesh_selfx_ws_bytes(int batch, int64_t total_verts, int64_t total_faces, int bins);
+int ofx_mesh_selfx(const float* verts, const int32_t* faces, const int64_t* vert_off, const int64_t* tri_off, int batch,
+                   int64_t max_faces, int bins, int32_t* partners, int32_t* first, int64_t* pairs, void* ws,
+                   int32_t* status, void* stream);
+/* Measurement aid (tools/meshcheck_probe.py; not on the operator path), as ofx_mesh_query_set_counters: per wave of 64
+ * binned faces words[0] += bins visited (the bin's box meets the wave's), words[1] += triangles staged (members of
+ * those bins), words[2] += ordered (face, face) pairs that passed the box test and reached the pair rule (every
+ * unordered pair is judged from both sides).  NULL: counting off.  Sticky. */
+int ofx_mesh_selfx_set_counters(unsigned long long* words);
+
 /* ------------------------------------------------------------------ rendering (csrc/ofx_render.hip)
  * Shaded views of triangle meshes for the reference's FID image sets (utils/render_utils.py:14-23, utils/render/):
  * a deterministic renderer of the project's own, parity with pyrender unpinned; tests/render_oracle.py

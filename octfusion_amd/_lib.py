@@ -226,6 +226,14 @@ _SIGS = {
     'ofx_mesh_winding_ws_bytes': (c_sz, [c_i, c_l, c_l, c_l, c_i], False),
     'ofx_mesh_winding': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_l, c_l, c_i, c_f, c_p, c_p, c_p, c_p], True),
     'ofx_mesh_winding_set_counters': (c_i, [c_p], True),
+    'ofx_mesh_weld_ws_bytes': (c_sz, [c_i, c_l, c_l], False),
+    'ofx_mesh_weld': (c_i, [c_p, c_p, c_p, c_p, c_i, c_l, c_l, c_p, c_p, c_p, c_p, c_p], True),
+    'ofx_mesh_weld_extract': (c_i, [c_p, c_p, c_p, c_p, c_i, c_l, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_p], True),
+    'ofx_mesh_topology_ws_bytes': (c_sz, [c_i, c_l, c_l], False),
+    'ofx_mesh_topology': (c_i, [c_p, c_p, c_p, c_p, c_i, c_l, c_l, c_p, c_p, c_p, c_p, c_p, c_p], True),
+    'ofx_mesh_selfx_ws_bytes': (c_sz, [c_i, c_l, c_l, c_i], False),
+    'ofx_mesh_selfx': (c_i, [c_p, c_p, c_p, c_p, c_i, c_l, c_i, c_p, c_p, c_p, c_p, c_p, c_p], True),
+    'ofx_mesh_selfx_set_counters': (c_i, [c_p], True),
     'ofx_ray_cast_ws_bytes': (c_sz, [c_i, c_l, c_l, c_l, c_i], False),
     'ofx_ray_cast': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_l, c_l, c_f, c_f, c_i, c_i, c_p, c_p, c_p, c_p, c_p,
                            c_p, c_p], True),

@@ -239,6 +239,10 @@ def run(args, rank, local_rank, world, device):
     mesh_comps = {}
     mesh_stats = {}
     simple_counts = {}
+    checks = {}
+    check = getattr(args, 'check', False)
+    if check and not (mesh and args.out):
+        raise ValueError('--check needs --mesh and --out')
     kw = dict(mesh=True, mesh_level=args.mesh_level, mesh_scale=mesh_scale(args.config), points=points) if mesh else {}
     if clean:
         kw['mesh_clean'] = True
@@ -266,6 +270,11 @@ def run(args, rank, local_rank, world, device):
             mesh_comps[i] = int(k)
         for i, (v, f) in zip(idxs, out.get('simple_meshes', ())):
             simple_counts[i] = (int(v.shape[0]), int(f.shape[0]))
+        if check:
+            from . import mesh_check
+            written = out.get('simple_meshes', out['meshes'])
+            for r in mesh_check.reports([('%d.obj' % i, m) for i, m in zip(idxs, written)]):
+                checks[r['name']] = r
         for b, i in enumerate(idxs if 'mesh_stats' in out else ()):
             mesh_stats[i] = {k: int(v[b]) for k, v in out['mesh_stats'].items()}
     total = sum(dt for _, dt in done)
@@ -287,6 +296,11 @@ def run(args, rank, local_rank, world, device):
     if simple is not None:
         res['rank0_simple_vertices'] = [simple_counts[i][0] for i in res['rank0_indices']]
         res['rank0_simple_faces'] = [simple_counts[i][1] for i in res['rank0_indices']]
+    if check:
+        res['rank0_mesh_check'] = [checks['%d.obj' % i] for i in res['rank0_indices']]
+        if rank == 0:
+            with open(os.path.join(args.out, 'mesh_check.json'), 'w') as fh:
+                json.dump(res['rank0_mesh_check'], fh, indent=1)
     return res
 
 
@@ -326,6 +340,10 @@ def main(argv=None):
                     help='with --mesh: write <out>/<index>.obj simplified by vertex clustering on the device, N cells '
                          '(1 .. 1024) along the longest side of every mesh (the cleaned one under --clean); --points and '
                          '--views keep the full mesh, and the result line gains rank0_simple_vertices / _faces')
+    ap.add_argument('--check', action='store_true',
+                    help='with --mesh: check every written mesh on the device (mesh_check.check: closed, manifold, '
+                         'oriented, self-intersections, ...) and write the reports of rank 0 to <out>/mesh_check.json; '
+                         'the result line gains rank0_mesh_check; needs --out')
     ap.add_argument('--octree-mesh', action='store_true',
                     help='write the generated octree itself as a mesh of cubes, <out>/octree/<index>.obj (the '
                          'reference\'s export_octree) and, for a three-stage config, <out>/octree_large/<index>.obj; '
@@ -348,6 +366,8 @@ def main(argv=None):
         raise ValueError('--views needs --mesh and --out')
     if args.octree_mesh and not args.out:
         raise ValueError('--octree-mesh needs --out')
+    if args.check and not (args.mesh and args.out):
+        raise ValueError('--check needs --mesh and --out')
     rank, local_rank, world = dist.init()
     from . import _lib
     _lib.require_device()

@@ -17,7 +17,7 @@ restates them in float64.  Where this can differ from mesh2sdf:
     walks its own connectivity.
 
     python -m octfusion_amd.mesh2sdf --input model.obj ... --out data [--size 128] [--level 0.015] [--pointcloud]
-        [--no-fix] [--sign winding [--beta B]] [--seed 0]
+        [--no-fix] [--sign winding|auto [--beta B]] [--seed 0]
 """
 import argparse
 import os
@@ -25,7 +25,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib, mesh, mesh_query, metrics
+from . import _lib, mesh, mesh_check, mesh_query, metrics
 from ._lib import call, ptr, stream
 
 MESH_SCALE = 0.8           # tools/repair_mesh.py:127: the raw mesh is scaled into [-0.8, 0.8]^3
@@ -41,7 +41,7 @@ def _max_batch(size):
     return max(1, _INT32_MAX // size ** 3)          # keeps the lattice of one call below 2^31 values
 
 
-def mesh_to_sdf(meshes, size=128, signed=True, beta=0.0):
+def mesh_to_sdf(meshes, size=128, signed=True, beta=0.0, stats=None):
     """SDF lattices [B, S, S, S] (fp32 on the device, x slowest) of ``meshes``, a list of B
     ``(verts [V, 3] fp32, faces [F, 3] int32)`` device tensors as ``mesh.marching_cubes`` returns them.  Lattice point
     ``(i, j, k)`` sits at ``2 (i, j, k) / S - 1`` -- what ``marching_cubes(sdf, level, bbmin=-1, bbmax=1)`` and
@@ -52,6 +52,10 @@ def mesh_to_sdf(meshes, size=128, signed=True, beta=0.0):
     lattice point (``mesh_query.winding_number`` at its fp32 rounding, ``beta`` as there; exact by default) exceeds
     0.5 -- the sign for raw meshes that are open, self-intersecting or nested.  The lattice points are made on the
     device; further launches and host reads of status words only.
+    ``signed='auto'``: per mesh, ray parity iff ``mesh_check.check`` (on the welded mesh) finds it watertight and free
+    of self-intersections, else the winding number -- each lattice is, bit for bit, the one ``signed=True`` or
+    ``signed='winding'`` gives that mesh.  ``stats`` (optional dict) receives ``sign``, the rule taken per mesh
+    (``'parity'`` or ``'winding'``), and ``check``, the reports.
     Bitwise reproducible, and a shape's lattice does not depend on the batch it is in.
 
     One launch group (per ``(2^31 - 1) // S^3`` shapes) and one host read, the status words.  Raises ValueError naming
@@ -67,13 +71,33 @@ def mesh_to_sdf(meshes, size=128, signed=True, beta=0.0):
     for k, (v, f) in enumerate(meshes):
         if f.shape[0] == 0 or v.shape[0] == 0:
             raise ValueError('mesh_to_sdf: shape %d has no faces' % k)
+    if isinstance(signed, str) and signed == 'auto':
+        return _sign_by_check(meshes, size, beta, stats)
     by_winding = mesh_query._winding_rule(signed, 'mesh_to_sdf')
+    if stats is not None:
+        stats['sign'] = ['winding' if by_winding else ('parity' if signed else 'none')] * len(meshes)
     out = []
     g = _max_batch(size)
     for b0 in range(0, len(meshes), g):
         out.append(_group(meshes[b0:b0 + g], b0, size, signed and not by_winding))
     sdf = out[0] if len(out) == 1 else torch.cat(out)
     return _sign_by_winding(meshes, sdf, size, beta) if by_winding else sdf
+
+
+def _sign_by_check(meshes, size, beta, stats):
+    """``signed='auto'``: the meshes ``mesh_check`` finds sound go through ray parity in one call, the others through
+    the winding number in another (a shape's lattice does not depend on the batch it is in)."""
+    reports = mesh_check.check(meshes)
+    rule = ['parity' if mesh_check.ray_parity_is_sound(r) else 'winding' for r in reports]
+    if stats is not None:
+        stats['sign'] = rule
+        stats['check'] = reports
+    sdf = torch.empty(len(meshes), size, size, size, dtype=torch.float32, device=meshes[0][0].device)
+    for name, signed in (('parity', True), ('winding', 'winding')):
+        idx = [k for k, r in enumerate(rule) if r == name]
+        if idx:
+            sdf[idx] = mesh_to_sdf([meshes[k] for k in idx], size, signed=signed, beta=beta)
+    return sdf
 
 
 _WINDING_POINTS = 1 << 24          # lattice points of one winding call (192 MiB of queries)
@@ -135,13 +159,16 @@ def _to_device_mesh(vertices, faces):
             f.to(device=dev, dtype=torch.int32).reshape(-1, 3).contiguous())
 
 
-def compute(vertices, faces, size=128, fix=False, level=0.015, return_mesh=False, sign='parity', beta=0.0):
+def compute(vertices, faces, size=128, fix=False, level=0.015, return_mesh=False, sign='parity', beta=0.0,
+            stats=None):
     """mesh2sdf.compute with its argument order, so tools/repair_mesh.py:150 ports unchanged: ``vertices`` [V, 3] in
     [-1, 1]^3 and ``faces`` [F, 3] (numpy or tensors) -> the signed lattice [S, S, S] as a fp32 device tensor, and with
     ``return_mesh`` also the mesh ``(verts, faces)`` the lattice belongs to, as device tensors.
 
     fix=False: the signed lattice of the input as it is -- ``sign='parity'``: only meaningful for a watertight input;
-      ``sign='winding'``: ``mesh_to_sdf(signed='winding', beta=beta)``, meaningful for a raw mesh too.
+      ``sign='winding'``: ``mesh_to_sdf(signed='winding', beta=beta)``, meaningful for a raw mesh too;
+      ``sign='auto'``: ``mesh_to_sdf(signed='auto')`` -- parity iff ``mesh_check`` finds the input sound, else the
+      winding number; ``stats`` (optional dict) receives the rule taken, as there.
     fix=True: the repair, composed from public calls only --
       1. ``u = mesh_to_sdf([input], size, signed=False)``, the unsigned distance;
       2. ``marching_cubes(u, level, bbmin=-1, bbmax=1)``: the surface at distance ``level`` around the input, an outer
@@ -150,13 +177,13 @@ def compute(vertices, faces, size=128, fix=False, level=0.015, return_mesh=False
       4. ``mesh_to_sdf([shell], size, signed=True)``, returned with the shell.
     So the repaired surface lies ``level`` outside the input, as mesh2sdf's does.  See the module docstring for where
     the result can differ from mesh2sdf's (marching-cubes table, components by shared vertex, exact far field)."""
-    if sign not in ('parity', 'winding'):
-        raise ValueError("compute: sign must be 'parity' or 'winding', got %r" % (sign,))
+    if sign not in ('parity', 'winding', 'auto'):
+        raise ValueError("compute: sign must be 'parity', 'winding' or 'auto', got %r" % (sign,))
     if fix and sign != 'parity':
         raise ValueError('compute: sign=%r needs fix=False (the repaired shell is watertight)' % (sign,))
     m = _to_device_mesh(vertices, faces)
     if not fix:
-        sdf = mesh_to_sdf([m], size, signed='winding' if sign == 'winding' else True, beta=beta)[0]
+        sdf = mesh_to_sdf([m], size, signed=True if sign == 'parity' else sign, beta=beta, stats=stats)[0]
         return (sdf, m) if return_mesh else sdf
     u = mesh_to_sdf([m], size, signed=False)
     shell = mesh.largest_component(mesh.marching_cubes(u, float(level), bbmin=-1, bbmax=1))[0]
@@ -265,10 +292,12 @@ def parser():
     ap.add_argument('--pointcloud', action='store_true', help='also draw the oriented point cloud of the saved mesh')
     ap.add_argument('--points', type=int, default=100000, help='points of the cloud')
     ap.add_argument('--no-fix', action='store_true', help='the input is watertight: take its signed lattice as it is')
-    ap.add_argument('--sign', choices=['parity', 'winding'], default='parity', help="'winding': the signed lattice "
-                    'of the raw mesh itself, signed by its winding number (implies --no-fix)')
+    ap.add_argument('--sign', choices=['parity', 'winding', 'auto'], default='parity', help="'winding': the signed "
+                    "lattice of the raw mesh itself, signed by its winding number; 'auto': by parity if mesh_check "
+                    'finds the mesh watertight and free of self-intersections, else by the winding number (both imply '
+                    '--no-fix)')
     ap.add_argument('--beta', type=float, default=mesh_query.DEFAULT_CLI_BETA, help='far-field opening of --sign '
-                    'winding (0: exact)')
+                    'winding / auto (0: exact)')
     ap.add_argument('--seed', type=int, default=0)
     return ap
 
@@ -280,8 +309,8 @@ def main(argv=None):
     for path in args.input:
         prepare_mesh(path, shape_name(path), os.path.join(root, 'sdf'), os.path.join(root, 'mesh'),
                      os.path.join(root, 'bbox'), os.path.join(root, 'dataset') if args.pointcloud else None,
-                     args.size, args.level, args.points, args.seed, fix=not (args.no_fix or args.sign == 'winding'),
-                     sign=args.sign, beta=args.beta if args.sign == 'winding' else 0.0)
+                     args.size, args.level, args.points, args.seed, fix=not (args.no_fix or args.sign != 'parity'),
+                     sign=args.sign, beta=args.beta if args.sign != 'parity' else 0.0)
     print('mesh2sdf: %d shapes written under %s' % (len(args.input), root))
 
 

@@ -174,6 +174,9 @@ def main(argv=None):
     ap.add_argument('--error', type=int, nargs='?', const=100000, default=None, metavar='N',
                     help='add mesh_query.mesh_error(input, output, N) per mesh to the report: how far the surface '
                          'moved, measured exactly against the triangles (N samples per side, default 100000)')
+    ap.add_argument('--check', action='store_true',
+                    help='print the mesh_check.check report of every output (clustering can leave non-manifold edges '
+                         'and folded faces behind), one JSON line each before the result line, which gains "check"')
     args = ap.parse_args(argv)
     if args.error is not None and args.error < 1:
         raise ValueError('simplify: --error needs at least one sample')
@@ -204,6 +207,11 @@ def main(argv=None):
         from . import mesh_query
         res['error'] = [mesh_query.mesh_error(m, o, args.error) if m[1].shape[0] and o[1].shape[0] else None
                         for m, o in zip(meshes, out)]
+    if args.check:
+        from . import mesh_check
+        res['check'] = mesh_check.reports(zip(names, out))
+        for r in res['check']:
+            print(json.dumps(r))
     print(json.dumps(res))
     return res
 
