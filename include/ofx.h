@@ -1343,6 +1343,54 @@ int ofx_mesh_selfx(const float* verts, const int32_t* faces, const int64_t* vert
  * unordered pair is judged from both sides).  NULL: counting off.  Sticky. */
 int ofx_mesh_selfx_set_counters(unsigned long long* words);
 
+/* ------------------------------------------------------------------ mesh as a graph, fairing, vertex normals
+ * (csrc/ofx_meshsmooth.hip).  tests/smooth_oracle.py restates the contract in float64.  Meshes, status words, limits
+ * and refusals as for the mesh checks above, with 1 <= total_verts <= 2^30 and 1 <= 6 total_faces <= 2^30.  A face
+ * TAKES PART iff its shape's status is zero and its three indices differ; every other face, and a vertex no such face
+ * uses (it may hold NaN), takes part in nothing.  A corner is 3 face + k (face local to the shape).  No atomics; every
+ * floating-point sum below is fp64, every operation rounded on its own, in the order stated.  Every output is a pure
+ * function of each shape's own arrays, bitwise, alone or anywhere in a batch, from run to run.  No host
+ * synchronisation.  A refused shape has empty rows and corner lists; its vflags, normals and out rows are unwritten.
+ *
+ * ofx_mesh_adjacency: row_off [V + 1] int64 over the vertices of the whole call, row_off[0] = 0; nbr (room for
+ *   6 total_faces) int32: row i = nbr[row_off[i] .. row_off[i + 1]) = the distinct vertices that share a face with i,
+ *   as indices of the shape, ascending.  vflags [V] int32: bit 0 = a face uses the vertex, bit 1 = it ends an edge
+ *   with exactly one face (boundary), bit 2 = it ends an edge with three or more.  corner_off [V + 1] int64 and
+ *   corner [3 total_faces] int32 (both, or both NULL): the corners at vertex i, ascending.
+ *
+ * ofx_mesh_vertex_normals: normals [V, 3] fp32.  With a, b, c the face's vertices in stored order, n = (b - a) x
+ *   (c - a) (differences first); a face with n exactly zero adds nothing.  The term of a corner at vertex p with the
+ *   next and previous vertices q, r of its face, u = q - p, w = r - p:  mode 0 (area) n;  2 (uniform) n / |n|;
+ *   1 (angle) (n / |n|) * atan2(|u x w|, u . w)  -- the division first, component by component; |x| =
+ *   sqrt((x0 x0 + x1 x1) + x2 x2).  The terms are added in corner order; the sum s gives s / |s| rounded to fp32 once,
+ *   or (0, 0, 0) when |s| is not positive.
+ *
+ * ofx_mesh_smooth: weights 0 uniform / 1 cotangent; boundary 0 fixed / 1 slide / 2 free; lambda, mu finite; iters
+ *   in [0, 10000].  out [V, 3] fp32; out64 [V, 3] fp64 (may be NULL).  The state is fp64, the input widened exactly;
+ *   an iteration is the half-step with s = lambda, then, unless mu == 0, the one with s = mu; a half-step sets, for
+ *   every moving vertex i with a positive weight sum,
+ *       p_i <- p_i + s * (A / W),  A = sum_j w_ij * (p_j - p_i),  W = sum_j w_ij,
+ *   j over row i ascending, all p from before the half-step.  w_ij = 1 (uniform) or max(0, sum / 2) with sum = the
+ *   cotangents, added in the order of i's corners, of the angle opposite the edge in every face on it: with o the
+ *   face's third vertex, u = p_i - p_o, w = p_j - p_o, cot = (u . w) / |u x w|, or 0 when |u x w| is not positive;
+ *   computed once, from the input.  A vertex moves iff a face uses it and, when it is a boundary vertex (bit 1):
+ *   fixed -- never; slide -- with w_ij = 1 for the neighbours on a one-face edge and 0 for the others, whatever
+ *   `weights`; free -- like any other.  out = the state rounded to fp32 once; a vertex that may not move (not used by
+ *   a face, or fixed) keeps its input bits in out and has the widened input in out64.
+ *   The launches: the adjacency, the rules, the weights, one per half-step, the rounding. */
+size_t ofx_mesh_adjacency_ws_bytes(int batch, int64_t total_verts, int64_t total_faces);
+int ofx_mesh_adjacency(const float* verts, const int32_t* faces, const int64_t* vert_off, const int64_t* tri_off,
+                       int batch, int64_t total_verts, int64_t total_faces, int64_t* row_off, int32_t* nbr,
+                       int32_t* vflags, int64_t* corner_off, int32_t* corner, void* ws, int32_t* status, void* stream);
+size_t ofx_mesh_vertex_normals_ws_bytes(int batch, int64_t total_verts, int64_t total_faces);
+int ofx_mesh_vertex_normals(const float* verts, const int32_t* faces, const int64_t* vert_off, const int64_t* tri_off,
+                            int batch, int64_t total_verts, int64_t total_faces, int mode, float* normals, void* ws,
+                            int32_t* status, void* stream);
+size_t ofx_mesh_smooth_ws_bytes(int batch, int64_t total_verts, int64_t total_faces, int weights);
+int ofx_mesh_smooth(const float* verts, const int32_t* faces, const int64_t* vert_off, const int64_t* tri_off,
+                    int batch, int64_t total_verts, int64_t total_faces, int weights, int boundary, double lambda,
+                    double mu, int iters, float* out, double* out64, void* ws, int32_t* status, void* stream);
+
 /* ------------------------------------------------------------------ rendering (csrc/ofx_render.hip)
  * Shaded views of triangle meshes for the reference's FID image sets (utils/render_utils.py:14-23, utils/render/):
  * a deterministic renderer of the project's own, parity with pyrender unpinned; tests/render_oracle.py

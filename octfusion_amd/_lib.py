@@ -234,6 +234,12 @@ _SIGS = {
     'ofx_mesh_selfx_ws_bytes': (c_sz, [c_i, c_l, c_l, c_i], False),
     'ofx_mesh_selfx': (c_i, [c_p, c_p, c_p, c_p, c_i, c_l, c_i, c_p, c_p, c_p, c_p, c_p, c_p], True),
     'ofx_mesh_selfx_set_counters': (c_i, [c_p], True),
+    'ofx_mesh_adjacency_ws_bytes': (c_sz, [c_i, c_l, c_l], False),
+    'ofx_mesh_adjacency': (c_i, [c_p, c_p, c_p, c_p, c_i, c_l, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p], True),
+    'ofx_mesh_vertex_normals_ws_bytes': (c_sz, [c_i, c_l, c_l], False),
+    'ofx_mesh_vertex_normals': (c_i, [c_p, c_p, c_p, c_p, c_i, c_l, c_l, c_i, c_p, c_p, c_p, c_p], True),
+    'ofx_mesh_smooth_ws_bytes': (c_sz, [c_i, c_l, c_l, c_i], False),
+    'ofx_mesh_smooth': (c_i, [c_p, c_p, c_p, c_p, c_i, c_l, c_l, c_i, c_i, c_d, c_d, c_i, c_p, c_p, c_p, c_p, c_p], True),
     'ofx_ray_cast_ws_bytes': (c_sz, [c_i, c_l, c_l, c_l, c_i], False),
     'ofx_ray_cast': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_l, c_l, c_f, c_f, c_i, c_i, c_p, c_p, c_p, c_p, c_p,
                            c_p, c_p], True),

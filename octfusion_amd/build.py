@@ -24,7 +24,7 @@ SOURCES = ['ofx_octree.hip', 'ofx_graph.hip', 'ofx_gemm.hip', 'ofx_gemm2.hip', '
            'ofx_mesh.hip', 'ofx_mesh_cc.hip', 'ofx_metrics.hip', 'ofx_voxmesh.hip', 'ofx_sdfdata.hip',
            'ofx_mesh2sdf.hip', 'ofx_train.hip', 'ofx_render.hip', 'ofx_nnsearch.hip',
            'ofx_simplify.hip', 'ofx_fieldmesh.hip', 'ofx_normals.hip', 'ofx_tribins.hip', 'ofx_meshquery.hip',
-           'ofx_raycast.hip', 'ofx_winding.hip', 'ofx_meshcheck.hip']
+           'ofx_raycast.hip', 'ofx_winding.hip', 'ofx_meshcheck.hip', 'ofx_meshsmooth.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC']
 
 

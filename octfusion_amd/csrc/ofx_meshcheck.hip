@@ -15,91 +15,19 @@
 //             twice, once from either side, by one function of the ordered pair (the lower index first): counts and
 //             minima only, so bins and order decide what is skipped and nothing else.
 // Integer atomics only count; no floating-point atomics.
-#include "ofx_tribins.h"
-
-#include <cmath>
-
 #pragma clang fp contract(off)
 
-#include "ofx_tri.h"
+#include "ofx_meshtopo.h"
 
 namespace {
 
-constexpr int MC_T = 256;
 constexpr int MC_K = OFX_MESH_TOPOLOGY_K;
-constexpr int64_t MC_NONE = INT64_MAX;        // key of a half-edge or a face that takes no part: sorts last
-constexpr int64_t MC_MAX_V = int64_t(1) << 30;             // what one ofx_points_sort takes
 constexpr int64_t MC_MAX_F = (int64_t(1) << 30) / 3;
 
 enum { C_DEG, C_EDGES, C_BOUNDARY, C_NONMANIFOLD, C_INCONSISTENT, C_DUPLICATE, C_ZERO_AREA, C_UNREF, C_COMPONENTS };
 
 bool mc_args_ok(int batch, int64_t V, int64_t F) {
   return batch >= 1 && batch <= 65535 && V >= 1 && V <= MC_MAX_V && F >= 1 && F <= MC_MAX_F;
-}
-
-struct McMesh {
-  const float* verts;
-  const int32_t* faces;
-  const int64_t* vert_off;
-  const int64_t* tri_off;
-  int batch;
-  int64_t V, F;
-};
-
-// The (key, index) arrays of a sort of n items and its workspace.
-struct McSort {
-  int64_t *key, *skey;
-  int32_t *idx, *sidx;
-  void* ws;
-  size_t ws_bytes;
-};
-
-struct Carver {
-  char* base;
-  size_t at = 0;
-  char* take(size_t bytes) {
-    char* p = base ? base + at : nullptr;
-    at += tb_align(bytes);
-    return p;
-  }
-  McSort sort(int64_t n) {
-    McSort s;
-    s.key = (int64_t*)take(n * sizeof(int64_t));
-    s.skey = (int64_t*)take(n * sizeof(int64_t));
-    s.idx = (int32_t*)take(n * sizeof(int32_t));
-    s.sidx = (int32_t*)take(n * sizeof(int32_t));
-    s.ws_bytes = ofx_points_sort_ws_bytes(n);
-    s.ws = take(s.ws_bytes);
-    return s;
-  }
-};
-
-int mc_sort(const McSort& s, int64_t n, void* stream) {
-  return ofx_points_sort(s.key, s.idx, n, s.skey, s.sidx, s.ws, s.ws_bytes, stream);
-}
-
-// The status words of a call: the validation of the shared bin builder, which stops there (no queries).
-size_t mc_status_layout(int batch, char* base, TbBins* w) {
-  return ofx_tribins_layout(batch, 0, 0, 1, base, w, nullptr);
-}
-int mc_status(const McMesh& m, const TbBins& w, int32_t* status, void* stream) {
-  const TbMesh t{m.verts, m.faces, m.vert_off, m.tri_off, m.batch, 1, tb_stride(1)};
-  return ofx_tribins_build(t, w, 0, status, stream);
-}
-
-// the three indices of face t of shape b; false if one lies outside the shape
-__device__ __forceinline__ bool mc_face(const McMesh& m, int64_t t, int b, int32_t (&id)[3]) {
-  const int64_t nv = m.vert_off[b + 1] - m.vert_off[b];
-  bool ok = true;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    id[k] = m.faces[t * 3 + k];
-    ok = ok && id[k] >= 0 && (int64_t)id[k] < nv;
-  }
-  return ok;
-}
-__device__ __forceinline__ bool mc_degenerate(const int32_t (&id)[3]) {
-  return id[0] == id[1] || id[1] == id[2] || id[0] == id[2];
 }
 
 // ---- weld ---------------------------------------------------------------------------------------------------------
@@ -262,18 +190,6 @@ __global__ __launch_bounds__(MC_T) void tp_init_kernel(McMesh m, TopoWs w) {
   for (int64_t i = m.V + (int64_t)blockIdx.x * MC_T + threadIdx.x; i < (int64_t)m.batch * MC_K; i += stride)
     w.acc[i] = 0ull;
 }
-
-// (b - a) x (c - a) of the nine coordinates is exactly zero: the rule of ofx_mesh_winding
-__device__ __forceinline__ void mc_normal(const float (&c)[9], double (&n)[3]) {
-  double e1[3], e2[3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    e1[a] = (double)c[3 + a] - (double)c[a];
-    e2[a] = (double)c[6 + a] - (double)c[a];
-  }
-  ms_cross(e1, e2, n);
-}
-__device__ __forceinline__ bool mc_flat(const double (&n)[3]) { return n[0] == 0.0 && n[1] == 0.0 && n[2] == 0.0; }
 
 // The three half-edges of every face: key = lower vertex << 31 | higher vertex (indices of the whole call, so a key
 // names its shape too), payload = half-edge << 1 | (the face walks it from the higher to the lower vertex).

@@ -83,7 +83,8 @@ def prepare(config, rank, device, ckpt=None, vae_ckpt=None, with_vae=True, allow
 def generate(net, cfg, n_shapes, rank, world, seed=0, ddim_steps=200, label=None, vae=None, out_dir=None,
              shapes_per_call=1, use_graph=None, sdf_resolution=None, timings=None, mesh=False, mesh_level=0.0,
              mesh_scale=1.0, points=None, mesh_clean=False, octree_mesh=False, views=False, view_size=299,
-             view_samples=1, mesh_simplify=None, field_mesh=False, mesh_margin=1):
+             view_samples=1, mesh_simplify=None, field_mesh=False, mesh_margin=1, mesh_smooth=None,
+             smooth_normals=False):
     """Yields (result indices, output dict, seconds) for every group of shapes this rank owns.  mesh: also
     out['meshes'] (needs the VAE and sdf_resolution), written as <out_dir>/<index>.obj.  points (needs mesh): also
     out['points'] = {position in the group: [points, 3] cloud} of every non-empty mesh, sampled on the device after the
@@ -100,7 +101,15 @@ def generate(net, cfg, n_shapes, rank, world, seed=0, ddim_steps=200, label=None
     mesh; out['meshes'], the clouds and the views stay those of the full mesh.
     field_mesh (needs mesh): the meshes come from mesh.field_mesh (octree-guided bricks, sdf_resolution up to 2048,
     mesh_margin finest octree cells around the finest nodes) instead of the dense sweep: out['mesh_stats'] holds the
-    per-shape seeds / bricks / leaks / total_bricks, and there is no out['sdfs'], hence no sdf.pt."""
+    per-shape seeds / bricks / leaks / total_bricks, and there is no out['sdfs'], hence no sdf.pt.
+    mesh_smooth=K (needs mesh): out['meshes'] are the meshes (the cleaned ones under mesh_clean) after K Taubin
+    iterations (mesh_smooth.smooth), before any simplification; clouds, views and files are the smoothed mesh's.
+    smooth_normals (needs mesh_smooth): also out['normals'], the angle-weighted vertex normals of every written
+    mesh (None for an empty one), written as vn lines."""
+    if mesh_smooth is not None and not mesh:
+        raise ValueError('mesh_smooth needs mesh')
+    if smooth_normals and mesh_smooth is None:
+        raise ValueError('smooth_normals needs mesh_smooth')
     if field_mesh and not mesh:
         raise ValueError('field_mesh needs mesh')
     if mesh_clean and not mesh:
@@ -123,6 +132,7 @@ def generate(net, cfg, n_shapes, rank, world, seed=0, ddim_steps=200, label=None
                         timings=timings, mesh=mesh, mesh_level=mesh_level, mesh_scale=mesh_scale,
                         **({'mesh_clean': True} if mesh_clean else {}),
                         **({'field_mesh': True, 'mesh_margin': mesh_margin} if field_mesh else {}),
+                        **({'mesh_smooth': mesh_smooth} if mesh_smooth is not None else {}),
                         **({'octree_mesh': True} if octree_mesh else {}))
         if dev.type == 'cuda':
             torch.cuda.synchronize()
@@ -136,6 +146,8 @@ def generate(net, cfg, n_shapes, rank, world, seed=0, ddim_steps=200, label=None
         if mesh_simplify is not None:
             from . import simplify
             out['simple_meshes'] = simplify.simplify(out['meshes'], cells=mesh_simplify)
+        if smooth_normals:
+            out['normals'] = written_normals(out.get('simple_meshes', out['meshes']))
         if out_dir is not None:
             write_outputs(out_dir, idxs, out, cfg)
         yield idxs, out, dt
@@ -161,6 +173,17 @@ def render_views(meshes, size=299, samples=1):
         return {}
     images = render.render([meshes[b] for b in keep], size=size, samples=samples)
     return {b: images[j] for j, b in enumerate(keep)}
+
+
+def written_normals(meshes):
+    """Per mesh the angle-weighted vertex normals (mesh_smooth.vertex_normals), None for a mesh without faces."""
+    from . import mesh_smooth
+    keep = [b for b, (_, f) in enumerate(meshes) if f.shape[0] > 0]
+    res = [None] * len(meshes)
+    if keep:
+        for b, n in zip(keep, mesh_smooth.vertex_normals([meshes[b] for b in keep])):
+            res[b] = n
+    return res
 
 
 def write_outputs(out_dir, idxs, out, cfg):
@@ -191,7 +214,8 @@ def write_outputs(out_dir, idxs, out, cfg):
             torch.save(out['sdfs'][b].cpu(), os.path.join(d, 'sdf.pt'))
         if 'meshes' in out:
             from . import mesh
-            mesh.write_obj(os.path.join(out_dir, '%d.obj' % i), *out.get('simple_meshes', out['meshes'])[b])
+            mesh.write_obj(os.path.join(out_dir, '%d.obj' % i), *out.get('simple_meshes', out['meshes'])[b],
+                           **({'normals': out['normals'][b]} if 'normals' in out else {}))
         for key, sub in (('octree_meshes', 'octree'), ('octree_meshes_large', 'octree_large')):
             if key in out:
                 from . import mesh
@@ -251,6 +275,15 @@ def run(args, rank, local_rank, world, device):
     if field:
         kw['field_mesh'] = True
         kw['mesh_margin'] = getattr(args, 'mesh_margin', 1)
+    smooth = getattr(args, 'smooth', None)
+    if smooth is not None:
+        if not mesh or not 0 <= smooth <= 10000:
+            raise ValueError('--smooth needs --mesh and 0 <= K <= 10000')
+        kw['mesh_smooth'] = smooth
+    if getattr(args, 'smooth_normals', False):
+        if smooth is None:
+            raise ValueError('--smooth-normals needs --smooth')
+        kw['smooth_normals'] = True
     if getattr(args, 'views', False):
         if not mesh or not args.out:
             raise ValueError('--views needs --mesh and --out')
@@ -304,7 +337,7 @@ def run(args, rank, local_rank, world, device):
     return res
 
 
-def main(argv=None):
+def parser():
     ap = argparse.ArgumentParser()
     ap.add_argument('--config', default='snet_uncond', choices=sorted(configs.CONFIGS))
     ap.add_argument('--shapes', type=int, default=8)
@@ -340,6 +373,12 @@ def main(argv=None):
                     help='with --mesh: write <out>/<index>.obj simplified by vertex clustering on the device, N cells '
                          '(1 .. 1024) along the longest side of every mesh (the cleaned one under --clean); --points and '
                          '--views keep the full mesh, and the result line gains rank0_simple_vertices / _faces')
+    ap.add_argument('--smooth', type=int, default=None, metavar='K',
+                    help='with --mesh: K Taubin iterations (mesh_smooth.smooth: lambda 0.5, mu -0.53, uniform weights) '
+                         'on every mesh, after --clean and before --simplify; the .obj, the clouds, the views and '
+                         '--check are the smoothed mesh\'s')
+    ap.add_argument('--smooth-normals', action='store_true',
+                    help='with --smooth: write the angle-weighted vertex normals of every mesh as vn lines')
     ap.add_argument('--check', action='store_true',
                     help='with --mesh: check every written mesh on the device (mesh_check.check: closed, manifold, '
                          'oriented, self-intersections, ...) and write the reports of rank 0 to <out>/mesh_check.json; '
@@ -355,13 +394,21 @@ def main(argv=None):
     ap.add_argument('--view-size', type=int, default=299, help='image size of --views (Inception v3: 299)')
     ap.add_argument('--view-samples', type=int, default=1, choices=(1, 4, 16),
                     help='samples per pixel of --views (render.render samples=; 4 is recommended for FID image sets)')
-    args = ap.parse_args(argv)
+    return ap
+
+
+def main(argv=None):
+    args = parser().parse_args(argv)
     if args.clean and not args.mesh:
         raise ValueError('--clean needs --mesh')
     if args.simplify is not None and not args.mesh:
         raise ValueError('--simplify needs --mesh')
     if args.field_mesh and not args.mesh:
         raise ValueError('--field-mesh needs --mesh')
+    if args.smooth is not None and not args.mesh:
+        raise ValueError('--smooth needs --mesh')
+    if args.smooth_normals and args.smooth is None:
+        raise ValueError('--smooth-normals needs --smooth')
     if args.views and not (args.mesh and args.out):
         raise ValueError('--views needs --mesh and --out')
     if args.octree_mesh and not args.out:

@@ -517,15 +517,21 @@ def _components(verts, faces, nv, nf):
     return res
 
 
-def write_obj(path, verts, faces):
+def write_obj(path, verts, faces, normals=None):
     """Write one mesh as OBJ -- ``v x y z`` lines, then 1-based ``f a b c`` lines (the layout trimesh's export of the
-    reference writes; coordinates with 9 significant digits, which round-trip fp32 exactly).  Vectorised: one
-    formatting call per block.  An empty mesh (no faces) writes no file and warns; returns whether a file was
-    written."""
+    reference writes; coordinates with 9 significant digits, which round-trip fp32 exactly).  With ``normals``
+    ([V, 3], one per vertex): ``vn x y z`` lines after the vertices and faces as ``f a//a b//b c//c``; without, the
+    file is what it always was.  Vectorised: one formatting call per block.  An empty mesh (no faces) writes no file
+    and warns; returns whether a file was written."""
     v = verts.detach().cpu().numpy() if torch.is_tensor(verts) else np.asarray(verts)
     f = faces.detach().cpu().numpy() if torch.is_tensor(faces) else np.asarray(faces)
     v = np.ascontiguousarray(v, np.float64).reshape(-1, 3)
     f = np.ascontiguousarray(f, np.int64).reshape(-1, 3) + 1
+    if normals is not None:
+        n = normals.detach().cpu().numpy() if torch.is_tensor(normals) else np.asarray(normals)
+        n = np.ascontiguousarray(n, np.float64).reshape(-1, 3)
+        if len(n) != len(v):
+            raise ValueError('write_obj: %d normals for %d vertices' % (len(n), len(v)))
     if len(f) == 0:
         warnings.warn('write_obj: empty mesh, %s not written' % path)
         return False
@@ -536,9 +542,15 @@ def write_obj(path, verts, faces):
         for lo in range(0, len(v), 1 << 16):
             blk = v[lo:lo + (1 << 16)]
             fh.write(('v %.9g %.9g %.9g\n' * len(blk)) % tuple(blk.ravel().tolist()))
+        for lo in range(0, len(v) if normals is not None else 0, 1 << 16):
+            blk = n[lo:lo + (1 << 16)]
+            fh.write(('vn %.9g %.9g %.9g\n' * len(blk)) % tuple(blk.ravel().tolist()))
         for lo in range(0, len(f), 1 << 16):
             blk = f[lo:lo + (1 << 16)]
-            fh.write(('f %d %d %d\n' * len(blk)) % tuple(blk.ravel().tolist()))
+            if normals is not None:
+                fh.write(('f %d//%d %d//%d %d//%d\n' * len(blk)) % tuple(np.repeat(blk.ravel(), 2).tolist()))
+            else:
+                fh.write(('f %d %d %d\n' * len(blk)) % tuple(blk.ravel().tolist()))
     return True
 
 

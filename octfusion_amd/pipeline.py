@@ -135,7 +135,7 @@ class CascadeSampler:
     def _sample_once(self, batch_size, ddim_steps=200, label=None, split_small=None, noises=None, sdf_resolution=None,
                      sdf_scale=0.9, use_graph=None, seed=None, save_index=0, shape_indices=None, timings=None,
                      mesh=False, mesh_level=0.0, mesh_scale=1.0, mesh_clean=False, octree_mesh=False,
-                     field_mesh=False, mesh_margin=1):
+                     field_mesh=False, mesh_margin=1, mesh_smooth=None):
         """Returns a dict with the per-stage results.  `noises` (optional) = dict of explicit
         init / step noise tensors per stage for reproducible runs.  sdf_resolution (e.g. 256) adds
         out['sdfs'] [B, R, R, R] (needs the VAE).
@@ -158,7 +158,10 @@ class CascadeSampler:
         out['sdfs']; two host syncs.
         octree_mesh: also out['octree_meshes'] = per-shape (verts, faces) of the cubes of every node at the small depth
         (voxmesh.octree_mesh; the reference's export_octree, :376,403-422) and, for a 3-stage model,
-        out['octree_meshes_large'] at the large depth (octfusion_model_union_3t.py:191); one host sync each."""
+        out['octree_meshes_large'] at the large depth (octfusion_model_union_3t.py:191); one host sync each.
+        mesh_smooth=K (needs mesh): out['meshes'] (the cleaned ones under mesh_clean) after K Taubin iterations
+        (mesh_smooth.smooth's defaults: lambda 0.5, mu -0.53, uniform weights, fixed boundary), same faces; one more
+        host sync (the status words)."""
         import time as _time
         if field_mesh and not (sdf_resolution and mesh and self.vae is not None):
             raise ValueError('field_mesh needs the VAE, sdf_resolution and mesh')
@@ -271,6 +274,17 @@ class CascadeSampler:
                     if mesh_clean:
                         out['mesh_components'] = cc['components']
                     t0 = lap('mesh', t0)
+        if mesh_smooth is not None:
+            if 'meshes' not in out:
+                raise ValueError('mesh_smooth needs mesh')
+            from . import mesh_smooth as _smooth
+            keep = [b for b, (_, f) in enumerate(out['meshes']) if f.shape[0] > 0]
+            if keep:
+                done = _smooth.smooth([out['meshes'][b] for b in keep], iterations=mesh_smooth)
+                out['meshes'] = list(out['meshes'])
+                for b, m in zip(keep, done):
+                    out['meshes'][b] = m
+            t0 = lap('mesh_smooth', t0)
         if timings is not None:
             timings.pop('_start', None)
         return out
